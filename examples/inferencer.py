@@ -41,6 +41,8 @@ def main():
                                           train=False,
                                           batch_size=args.batch_size)
     cfg = TrainingConfig(batch_size=args.batch_size)
+    # validate_model moves each batch to cfg.device; the model has to be there
+    model.to(cfg.device)
     stats = validate_model(model, loader, CrossEntropyLoss(), cfg)
     print(f"val loss {stats['loss']:.4f} acc {stats['accuracy']:.4f}")
 
