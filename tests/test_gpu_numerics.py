@@ -116,6 +116,221 @@ def test_gemm_tn(dtype, M, N, K):
     assert relerr(c, ref) < tol, relerr(c, ref)
 
 
+# ---- one small case per GEMM dispatch route --------------------------------
+# Shapes are the smallest that select each route in bindings.cpp::gemm /
+# gemm_nt / gemm_tn and the launchers in gemm.hip; the id names the route.
+# Every ext.gemm case checks three epilogues against the fp32 reference:
+#   lin_res   bias + residual, linear activation
+#   relu      bias + relu, no residual
+#   relu_res  relu(a@b + bias) + r with r = -3|randn|: adding r before the
+#             relu instead of after it is off by O(1), far past tolerance
+
+EPILOGUES = ("lin_res", "relu", "relu_res")
+
+
+def gemm_epilogue_err(dtype, M, N, K, variant):
+    """relerr of ext.gemm against the fp32 reference for one epilogue."""
+    torch.manual_seed(5)
+    a = torch.randn(M, K, dtype=dtype, device=DEV)
+    b = torch.randn(K, N, dtype=dtype, device=DEV)
+    bias = torch.randn(N, dtype=dtype, device=DEV)
+    ref = a.float() @ b.float() + bias.float()
+    act, r = 0, None
+    if variant == "lin_res":
+        r = torch.randn(M, N, dtype=dtype, device=DEV)
+    elif variant == "relu_res":
+        r = (-3 * torch.randn(M, N, device=DEV).abs()).to(dtype)
+    if variant != "lin_res":
+        act, ref = 1, ref.clamp_min(0)
+    if r is not None:
+        ref = ref + r.float()
+    c = ext.gemm(a, b, bias, act, r)
+    assert c.dtype == dtype and c.shape == (M, N)
+    return relerr(c, ref)
+
+
+def gemm_nt_err(dtype, M, N, K):
+    torch.manual_seed(6)
+    a = torch.randn(M, K, dtype=dtype, device=DEV)
+    b = torch.randn(N, K, dtype=dtype, device=DEV)
+    return relerr(ext.gemm_nt(a, b), a.float() @ b.float().t())
+
+
+def k_tol(dtype, K):
+    return TOL[dtype] * max(1, K // 128)
+
+
+BF16, F32 = torch.bfloat16, torch.float32
+GEMM_ROUTES = [
+    pytest.param(BF16, 128, 64, 64, id="bf16-nt32_z1"),
+    pytest.param(BF16, 128, 64, 256, id="bf16-nt32_z2_splitk_fin_ep"),
+    pytest.param(BF16, 128, 66, 256, id="bf16-nt32_z1_raggedN"),
+    pytest.param(BF16, 130, 70, 264, id="bf16-nt32_raggedMN"),
+    pytest.param(BF16, 32, 64, 64, id="bf16-k_gemm_nn_glds"),
+    pytest.param(BF16, 100, 10, 27, id="bf16-k_gemm_nn_scalar"),
+    pytest.param(BF16, 1, 65, 100, id="bf16-gemv_nn1_unsplit"),
+    pytest.param(BF16, 1, 768, 768, id="bf16-gemv_nn1_split_fin2"),
+    pytest.param(F32, 128, 64, 256, id="f32-nt_z_zf2_splitk_fin_ep"),
+    pytest.param(F32, 128, 64, 64, id="f32-nt_db"),
+    pytest.param(F32, 128, 66, 3080, id="f32-k_gemm_nt_glds_longK"),
+    pytest.param(F32, 32, 64, 64, id="f32-k_gemm_nn_glds"),
+    pytest.param(F32, 100, 10, 27, id="f32-k_gemm_nn_scalar"),
+    pytest.param(F32, 1, 65, 100, id="f32-gemv_nn1_unsplit"),
+    pytest.param(F32, 1, 768, 768, id="f32-gemv_nn1_split_fin2"),
+]
+
+
+@pytest.mark.parametrize("variant", EPILOGUES)
+@pytest.mark.parametrize("dtype,M,N,K", GEMM_ROUTES)
+def test_gemm_route_epilogue(dtype, M, N, K, variant):
+    err = gemm_epilogue_err(dtype, M, N, K, variant)
+    print(f"relerr {err:.3e} tol {k_tol(dtype, K):.3e}")
+    assert err < k_tol(dtype, K), (M, N, K, variant, err)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gemm_route_gemv_hugeK(dtype):
+    # M=1, K > 8192: legacy k_gemv_nn_part / k_gemv_nn_fin. No residual
+    # variants: the binding rejects a residual on this route.
+    M, N, K = 1, 65, 8200
+    torch.manual_seed(5)
+    a = torch.randn(M, K, dtype=dtype, device=DEV)
+    b = torch.randn(K, N, dtype=dtype, device=DEV)
+    bias = torch.randn(N, dtype=dtype, device=DEV)
+    ref = a.float() @ b.float() + bias.float()
+    assert relerr(ext.gemm(a, b, bias, 0), ref) < k_tol(dtype, K)
+    assert relerr(ext.gemm(a, b, bias, 1), ref.clamp_min(0)) < k_tol(dtype, K)
+    with pytest.raises(RuntimeError, match="residual"):
+        ext.gemm(a, b, bias, 0, torch.zeros(M, N, dtype=dtype, device=DEV))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gemm_rejects_mismatched_bias(dtype):
+    a = torch.randn(32, 64, dtype=dtype, device=DEV)
+    b = torch.randn(64, 64, dtype=dtype, device=DEV)
+    other = F32 if dtype == BF16 else BF16
+    with pytest.raises(RuntimeError, match="bias"):
+        ext.gemm(a, b, torch.zeros(64, dtype=other, device=DEV), 0)
+    with pytest.raises(RuntimeError, match="bias"):
+        ext.gemm(a, b, torch.zeros(63, dtype=dtype, device=DEV), 0)
+    with pytest.raises(RuntimeError, match="bias"):
+        ext.gemm(a, b, torch.zeros(128, dtype=dtype, device=DEV)[::2], 0)
+
+
+@pytest.mark.parametrize("dtype,M,N,K", [
+    pytest.param(BF16, 128, 64, 512, id="bf16-nt32_split"),
+    pytest.param(F32, 128, 64, 512, id="f32-nt_z_splitk_reduce"),
+    pytest.param(BF16, 64, 27, 130, id="bf16-k_gemm_nt_scalar"),
+    pytest.param(F32, 64, 27, 130, id="f32-k_gemm_nt_scalar"),
+    pytest.param(BF16, 1, 100, 33, id="bf16-gemv_nt"),
+    pytest.param(F32, 1, 100, 33, id="f32-gemv_nt"),
+])
+def test_gemm_nt_route(dtype, M, N, K):
+    err = gemm_nt_err(dtype, M, N, K)
+    print(f"relerr {err:.3e} tol {k_tol(dtype, K):.3e}")
+    assert err < k_tol(dtype, K), (M, N, K, err)
+
+
+@pytest.mark.parametrize("out_in_dt", [False, True])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,N,K", [
+    pytest.param(512, 64, 128, id="vec_slabs"),
+    pytest.param(130, 33, 27, id="scalar_kernel_scalar_reduce"),
+    pytest.param(4096, 64, 64, id="splitk_fold"),
+    pytest.param(256, 64, 128, id="splitk_reduce4"),
+])
+def test_gemm_tn_route(dtype, out_in_dt, M, N, K):
+    torch.manual_seed(7)
+    a = torch.randn(M, K, dtype=dtype, device=DEV)
+    b = torch.randn(M, N, dtype=dtype, device=DEV)
+    c = ext.gemm_tn(a, b, out_in_dt)
+    assert c.dtype == (dtype if out_in_dt else F32) and c.shape == (K, N)
+    err = relerr(c, a.float().t() @ b.float())
+    tol = TOL[dtype] * max(1, M // 256)
+    print(f"relerr {err:.3e} tol {tol:.3e}")
+    assert err < tol, (M, N, K, err)
+
+
+# bf16 16x16-tile routes, reachable only with TNN_GEMM32=0 (read once per
+# process): k_gemm_nt_db<bf16>, k_gemm_nt_z<bf16> + k_splitk_fin_ep<bf16>,
+# k_gemm<bf16,true,true>, and k_gemm_nt_z<bf16> + splitk_reduce for gemm_nt
+GEMM16_BF16_SHAPES = [(128, 64, 64), (128, 64, 256), (128, 66, 3080)]
+GEMM16_BF16_NT_SHAPE = (128, 64, 512)
+
+
+def gemm16_bf16_errs():
+    """Worst relerr per case; run by the child of the test below."""
+    out = {}
+    for M, N, K in GEMM16_BF16_SHAPES:
+        for v in EPILOGUES:
+            out[f"gemm-{M}x{N}x{K}-{v}"] = [gemm_epilogue_err(BF16, M, N, K, v),
+                                            k_tol(BF16, K)]
+    M, N, K = GEMM16_BF16_NT_SHAPE
+    out[f"gemm_nt-{M}x{N}x{K}"] = [gemm_nt_err(BF16, M, N, K), k_tol(BF16, K)]
+    return out
+
+
+def test_gemm_bf16_16x16_routes_fresh_process():
+    import json, os, subprocess, sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    child = ("import sys, json; sys.path[:0] = [%r, %r]; "
+             "import test_gpu_numerics as t; "
+             "print('ERRS ' + json.dumps(t.gemm16_bf16_errs()))"
+             % (os.path.dirname(here), here))
+    r = subprocess.run([sys.executable, "-c", child],
+                       env=dict(os.environ, TNN_GEMM32="0"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("ERRS ")][-1]
+    errs = json.loads(line[5:])
+    print(errs)
+    assert len(errs) == 3 * len(EPILOGUES) + 1
+    worst = max(errs, key=lambda k: errs[k][0] / errs[k][1])
+    assert errs[worst][0] < errs[worst][1], (worst, errs[worst])
+
+
+@pytest.mark.parametrize("M", [64, 1])
+def test_linear_nograd_gelu_residual_fuses(M):
+    # act + residual rides the GEMM epilogue under no_grad on every route
+    # (M=64: tile kernel; M=1: decode matvec)
+    import torch.nn.functional as F
+    from tnn_amd import ops
+    torch.manual_seed(8)
+    K = N = 64
+    x = torch.randn(M, K, dtype=BF16, device=DEV)
+    # weights as a model holds them: parameters that require grad
+    w = torch.nn.Parameter(torch.randn(K, N, dtype=BF16, device=DEV))
+    b = torch.nn.Parameter(torch.randn(N, dtype=BF16, device=DEV))
+    r = torch.randn(M, N, dtype=BF16, device=DEV)
+    with torch.no_grad():
+        y = ops.linear(x, w, b, act="gelu", residual=r)
+        yr = ops.linear(x, w, b, act="relu", residual=r)
+    ref_r = (x.float() @ w.float() + b.float()).clamp_min(0) + r.float()
+    assert relerr(yr, ref_r) < k_tol(BF16, K)
+    ref = F.gelu(x.float() @ w.float() + b.float(), approximate="tanh") \
+        + r.float()
+    assert relerr(y, ref) < k_tol(BF16, K)
+
+
+def test_linear_grad_relu_residual_still_rejected():
+    # with a backward to follow, relu + fused residual stays an error (the
+    # mask replay reads y, which would include the residual): ops.linear
+    # raises up front, a direct _Linear.apply raises in its backward
+    from tnn_amd import ops
+    from tnn_amd.ops.functional import _Linear
+    torch.manual_seed(9)
+    x = torch.randn(64, 64, dtype=BF16, device=DEV, requires_grad=True)
+    w = torch.randn(64, 64, dtype=BF16, device=DEV, requires_grad=True)
+    b = torch.randn(64, dtype=BF16, device=DEV)
+    r = torch.randn(64, 64, dtype=BF16, device=DEV)
+    assert torch.is_grad_enabled()
+    with pytest.raises(AssertionError, match="residual"):
+        ops.linear(x, w, b, act="relu", residual=r)
+    y = _Linear.apply(x, w, b, "relu", r)
+    with pytest.raises(AssertionError, match="residual"):
+        y.float().sum().backward()
+
+
 # ---------------------------------------------------------------------------
 # conv2d implicit GEMM (shapes from WRN-16-8 / ResNet-9; SURVEY §7)
 # ---------------------------------------------------------------------------

@@ -132,6 +132,24 @@ at::Tensor colsum(const at::Tensor& x) {
 }
 
 // ---- gemm ------------------------------------------------------------------
+// TNN_GEMM32=0 sends bf16 NT shapes to the 16x16-MFMA kernels instead of
+// the 32x32 one (read once per process)
+static bool gemm32_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("TNN_GEMM32");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// fp32 split-K slabs [z, rows*cols]; none (null) when unsplit
+static float* splitk_ws(at::Tensor& ws, const at::Tensor& like, int z,
+                        int64_t rows, int64_t cols, bool force = false) {
+  if (z <= 1 && !force) return nullptr;
+  ws = at::empty({(int64_t)z * rows * cols}, like.options().dtype(at::kFloat));
+  return ws.data_ptr<float>();
+}
+
 at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
                 const c10::optional<at::Tensor>& bias, int64_t act_kind,
                 const c10::optional<at::Tensor>& residual = c10::nullopt,
@@ -146,7 +164,15 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
               a.scalar_type(), " vs ", b.scalar_type());
   int M = a.size(0), K = a.size(1), N = b.size(1);
   auto c = at::empty({M, N}, a.options());
-  const void* bp = bias.has_value() ? bias->data_ptr() : nullptr;
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    // the kernels read bias as a's element type, N entries
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
+                bias->scalar_type() == a.scalar_type(),
+                "gemm bias must be contiguous [", N, "] ", a.scalar_type(),
+                ", got ", bias->sizes(), " ", bias->scalar_type());
+    bp = bias->data_ptr();
+  }
   const void* rp = nullptr;
   if (residual.has_value()) {
     TORCH_CHECK(residual->is_contiguous() &&
@@ -158,7 +184,7 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
   const float* lng = nullptr;
   const float* lnb = nullptr;
   if (ln_gamma.has_value()) {
-    TORCH_CHECK(M == 1 && K <= GEMV1_MAX_K_DECL && ln_beta.has_value() &&
+    TORCH_CHECK(M == 1 && K <= GEMV1_MAX_K && ln_beta.has_value() &&
                 ln_gamma->scalar_type() == at::kFloat &&
                 ln_beta->scalar_type() == at::kFloat,
                 "fused ln: decode GEMV only, fp32 gamma/beta");
@@ -166,16 +192,12 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
     lnb = ln_beta->data_ptr<float>();
   }
   if (M == 1) {
-    if (K <= GEMV1_MAX_K_DECL) {
+    if (K <= GEMV1_MAX_K) {
       // LDS-cached matvec; K-split across blocks to fill the chip (fp32
       // partials + a parallel finalize) when N alone is too narrow
       int ns = gemv_nn1_nsplit(N, K);
       at::Tensor part;
-      float* pp = nullptr;
-      if (ns > 1) {
-        part = at::empty({(int64_t)ns * N}, a.options().dtype(at::kFloat));
-        pp = part.data_ptr<float>();
-      }
+      float* pp = splitk_ws(part, a, ns, 1, N);
       gemv_nn1_launch(dt_of(a), a.data_ptr(), b.data_ptr(), bp, rp,
                       c.data_ptr(), pp, ns, lng, lnb, (float)ln_eps, N, K,
                       (int)act_kind, cur_stream());
@@ -191,38 +213,27 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
     return c;
   }
   bool vec_ok = (dt_of(a) == DT::F32 ? K % 4 == 0 : K % 8 == 0) &&
-                (((uintptr_t)a.data_ptr() & 15) == 0);
+                ptr_aligned16(a.data_ptr());
   if (M >= 64 && vec_ok) {
     // transpose the (weight-sized) B once and take the NT glds path: B rows
     // become k-contiguous LDS-DMA targets instead of a VGPR scatter
     auto bt = at::empty({(int64_t)N, (int64_t)K}, b.options());
     transpose_w_launch(dt_of(b), b.data_ptr(), bt.data_ptr(), 1, 1, K, N,
                        cur_stream());
-    static const bool use32 = [] {
-      const char* e = getenv("TNN_GEMM32");
-      return !(e && e[0] == '0');
-    }();
-    if (use32 && dt_of(a) == DT::BF16) {
+    at::Tensor ws;
+    if (gemm32_enabled() && dt_of(a) == DT::BF16) {
       // 32x32x16-MFMA tile core (peak issue at this kernel's 2
       // waves/SIMD residency; the 16x16x32 core needs 3-4)
       int z = N % 4 == 0 ? gemm_nt32_zsplits(M, N, K) : 1;
-      at::Tensor ws;
-      float* wp = nullptr;
-      if (z > 1) {
-        ws = at::empty({(int64_t)z * M * N}, a.options().dtype(at::kFloat));
-        wp = ws.data_ptr<float>();
-      }
-      gemm_nt32_launch(a.data_ptr(), bt.data_ptr(), wp, nullptr, bp, rp,
-                       c.data_ptr(), z, zero_page(a), M, N, K, (int)act_kind,
-                       cur_stream());
+      gemm_nt32_launch(a.data_ptr(), bt.data_ptr(), splitk_ws(ws, a, z, M, N),
+                       bp, rp, c.data_ptr(), z, zero_page(a), M, N, K,
+                       (int)act_kind, cur_stream());
       return c;
     }
     const int zf = N % 4 == 0 ? gemm_nt_fsplits(dt_of(a), M, N, K) : 1;
-    if (zf > 1 && K <= 3072 && ((uintptr_t)bt.data_ptr() & 15) == 0) {
-      auto ws = at::empty({(int64_t)zf * M * N},
-                          a.options().dtype(at::kFloat));
+    if (zf > 1 && K <= 3072 && ptr_aligned16(bt.data_ptr())) {
       gemm_nt_zf_launch(dt_of(a), a.data_ptr(), bt.data_ptr(),
-                        ws.data_ptr<float>(), bp, rp, c.data_ptr(), zf,
+                        splitk_ws(ws, a, zf, M, N), bp, rp, c.data_ptr(), zf,
                         zero_page(a), M, N, K, (int)act_kind, cur_stream());
       return c;
     }
@@ -245,32 +256,20 @@ at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& b) {
               "gemm_nt shapes ", a.sizes(), " @ ", b.sizes(), "^T");
   int M = a.size(0), K = a.size(1), N = b.size(0);
   auto c = at::empty({M, N}, a.options());
-  static const bool use32nt = [] {
-    const char* e = getenv("TNN_GEMM32");
-    return !(e && e[0] == '0');
-  }();
-  if (use32nt && dt_of(a) == DT::BF16 && K % 8 == 0 &&
-      ((uintptr_t)a.data_ptr() & 15) == 0 &&
-      ((uintptr_t)b.data_ptr() & 15) == 0) {
+  at::Tensor ws;
+  if (gemm32_enabled() && dt_of(a) == DT::BF16 && K % 8 == 0 &&
+      ptr_aligned16(a.data_ptr()) && ptr_aligned16(b.data_ptr())) {
     int z32 = N % 4 == 0 ? gemm_nt32_zsplits(M, N, K) : 1;
-    at::Tensor ws;
-    float* wp = nullptr;
-    if (z32 > 1) {
-      ws = at::empty({(int64_t)z32 * M * N}, a.options().dtype(at::kFloat));
-      wp = ws.data_ptr<float>();
-    }
-    gemm_nt32_launch(a.data_ptr(), b.data_ptr(), wp, nullptr, nullptr,
-                     nullptr, c.data_ptr(), z32, zero_page(a), M, N, K, 0,
-                     cur_stream());
+    gemm_nt32_launch(a.data_ptr(), b.data_ptr(), splitk_ws(ws, a, z32, M, N),
+                     /*bias=*/nullptr, /*resid=*/nullptr, c.data_ptr(), z32,
+                     zero_page(a), M, N, K, 0, cur_stream());
     return c;
   }
   int z = gemm_nt_zsplits(dt_of(a), M, N, K);
-  if (z > 1 && ((uintptr_t)a.data_ptr() & 15) == 0 &&
-      ((uintptr_t)b.data_ptr() & 15) == 0) {
+  if (z > 1 && ptr_aligned16(a.data_ptr()) && ptr_aligned16(b.data_ptr())) {
     // huge-K underfilled shape (vocab-head dgrad): K-split fp32 slabs
-    auto ws = at::empty({(int64_t)z * M * N}, a.options().dtype(at::kFloat));
     gemm_nt_z_launch(dt_of(a), a.data_ptr(), b.data_ptr(),
-                     ws.data_ptr<float>(), c.data_ptr(), dt_of(a), z,
+                     splitk_ws(ws, a, z, M, N), c.data_ptr(), dt_of(a), z,
                      zero_page(a), M, N, K, cur_stream());
     return c;
   }
@@ -294,11 +293,8 @@ at::Tensor gemm_tn(const at::Tensor& a, const at::Tensor& b, bool out_in_dt) {
                                  : a.options());
   int z = gemm_tn_zsplits(M, N, K);
   at::Tensor ws;
-  float* wsp = nullptr;
-  if (z > 1 || out_dt != DT::F32) {
-    ws = at::empty({(int64_t)z * K * N}, a.options().dtype(at::kFloat));
-    wsp = ws.data_ptr<float>();
-  }
+  // a cast output goes through the reduce (and so a slab) even unsplit
+  float* wsp = splitk_ws(ws, a, z, K, N, /*force=*/out_dt != DT::F32);
   gemm_tn_launch(dt_of(a), a.data_ptr(), b.data_ptr(), c.data_ptr(), out_dt,
                  wsp, z, zero_page(a), M, N, K, cur_stream());
   return c;

@@ -14,7 +14,179 @@ namespace tnn {
 using namespace tile;
 
 // ---------------------------------------------------------------------------
-// NN / NT kernel: C[M,N] = act(A[M,K] @ B + bias)
+// pieces shared by every route
+// ---------------------------------------------------------------------------
+
+// The one fused epilogue: act(v + bias[col]) + resid[row, col], all in
+// fp32 — the order of the eager path in ops/functional.py::linear. Null
+// bias / resid and ACT_LINEAR skip their step.
+template <typename T>
+struct Epilogue {
+  const T* bias;
+  const T* resid;
+  int ldc;  // row stride of resid
+  int act;
+  // resid addressed by flat element index (for callers that already
+  // hold row * ldc + col)
+  DEV float at(float v, int col, int64_t idx) const {
+    if (bias) v += VecIO<T>::to_f32(bias[col]);
+    if (act != ACT_LINEAR) v = act_apply(v, act);
+    if (resid) v += VecIO<T>::to_f32(resid[idx]);
+    return v;
+  }
+  DEV float operator()(float v, int row, int col) const {
+    return at(v, col, (int64_t)row * ldc + col);
+  }
+};
+
+// 16 bytes of row_base[idx .. idx+V): one vector load when the span is
+// inside [0, limit) and 16B-aligned, else element-wise with zero fill.
+template <typename T>
+DEV Pack16<T> load16_guarded(const T* row_base, int idx, int limit) {
+  constexpr int V = 16 / sizeof(T);
+  const T* src = row_base + idx;
+  Pack16<T> v = {};
+  if (idx + V <= limit && aligned16(src)) {
+    v = *(const Pack16<T>*)src;
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      if (idx + j < limit) v.e[j] = src[j];
+  }
+  return v;
+}
+
+// Stage ROWS k-contiguous rows src[row0 + r][k0 .. k0 + BK) (row stride K)
+// as the swizzled LDS image dst[r][k]; rows >= nrows and k >= K are zero.
+template <typename T, int ROWS>
+DEV void stage_rows(T* dst, const T* __restrict__ src, int row0, int nrows,
+                    int k0, int K) {
+  constexpr int V = 16 / sizeof(T);
+#pragma unroll
+  for (int c = threadIdx.x; c < ROWS * (BK / V); c += THREADS) {
+    int row = c / (BK / V);
+    int kk = (c % (BK / V)) * V;
+    int g = row0 + row;
+    Pack16<T> v = {};
+    if (g < nrows) v = load16_guarded(&src[(int64_t)g * K], k0 + kk, K);
+    *(Pack16<T>*)&dst[lds_off<T>(row, kk)] = v;
+  }
+}
+
+// The same image by LDS-DMA (K % V == 0, 16B-aligned src): rows >= nrows
+// and k >= k_hi read the zero page.
+template <typename T, int ROWS>
+DEV void glds_stage_rows(T* dst, const WaveCoord& wc,
+                         const T* __restrict__ src,
+                         const T* __restrict__ zero16, int row0, int nrows,
+                         int K, int k0, int k_hi) {
+  glds_stage<T, ROWS>(dst, wc, [&](int rl, int kk) -> const T* {
+    int g = row0 + rl, gk = k0 + kk;
+    if (g >= nrows || gk >= k_hi) return zero16;
+    return &src[(int64_t)g * K + gk];
+  });
+}
+
+// Stage src[k0 + k][c0 .. c0 + COLS) (row-major, ld columns, rows < k_end)
+// transposed, as the image dst[c][k]: column-contiguous vector loads,
+// element scatter into LDS.
+template <typename T, int COLS>
+DEV void stage_transposed(T* dst, const T* src, int ld, int k0,
+                          int k_end, int c0) {
+  constexpr int V = 16 / sizeof(T);
+#pragma unroll 1  // full unroll quadruples live address state (spills)
+  for (int c = threadIdx.x; c < BK * (COLS / V); c += THREADS) {
+    int kk = c / (COLS / V);
+    int cc = (c % (COLS / V)) * V;
+    int gk = k0 + kk;
+    Pack16<T> v = {};
+    if (gk < k_end) v = load16_guarded(&src[(int64_t)gk * ld], c0 + cc, ld);
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      dst[lds_off<T>(cc + j, kk)] = v.e[j];
+  }
+}
+
+// cast store of one 16x16-core block tile through the fused epilogue
+template <typename T>
+DEV void epilogue_store(const WaveCoord& wc, f32x4 acc[FM][FN], T* C, int m0,
+                        int n0, int M, int N, const Epilogue<T>& ep) {
+  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
+    if (row < M && col < N)
+      C[(int64_t)row * N + col] = VecIO<T>::from_f32(ep(v, row, col));
+  });
+}
+
+// fp32 slab store: block z owns slab z of the [gridDim.z][rows][cols]
+// workspace (the output itself when unsplit); a separate reduce pass sums
+// the slabs — deterministic, no atomic contention
+DEV void slab_store(const WaveCoord& wc, f32x4 acc[FM][FN], float* ws,
+                    int row0, int col0, int rows, int cols) {
+  float* out = ws + (int64_t)blockIdx.z * rows * cols;
+  epilogue_visit(wc, acc, row0, col0, [&](int row, int col, float v) {
+    if (row < rows && col < cols) out[(int64_t)row * cols + col] = v;
+  });
+}
+
+// this block's BK-aligned slice [k_lo, k_hi) of a K reduction split over
+// grid.z (the whole of K when gridDim.z == 1)
+DEV void ksplit_range(int K, int& k_lo, int& k_hi) {
+  const int Z = gridDim.z;
+  k_lo = (int)(((int64_t)K * blockIdx.z / Z) / BK * BK);
+  k_hi = blockIdx.z + 1 == Z
+             ? K
+             : (int)(((int64_t)K * (blockIdx.z + 1) / Z) / BK * BK);
+}
+
+// Double-buffered global_load_lds main loop over k in [k_lo, k_hi) for NT
+// operands (A[M,K] and B[N,K] rows are both k-contiguous, so the next
+// chunk's LDS-DMAs overlap the current chunk's MFMAs). Rows past M / N
+// and k past k_hi read the zero page. compute(As, Bs) consumes one
+// staged [BM][BK] x [BN][BK] chunk.
+template <typename T, typename Compute>
+DEV void nt_db_mainloop(const T* __restrict__ A, const T* __restrict__ B,
+                        const T* __restrict__ zero16, T (&As)[2][BM * BK],
+                        T (&Bs)[2][BN * BK], const WaveCoord& wc, int m0,
+                        int n0, int M, int N, int K, int k_lo, int k_hi,
+                        Compute&& compute) {
+  auto stage = [&](int kk0, int which) {
+    glds_stage_rows<T, BM>(As[which], wc, A, zero16, m0, M, K, kk0, k_hi);
+    glds_stage_rows<T, BN>(Bs[which], wc, B, zero16, n0, N, K, kk0, k_hi);
+  };
+  constexpr int NPER = glds_count<T, BM>() + glds_count<T, BN>();
+
+  const int nch = (k_hi - k_lo + BK - 1) / BK;
+  stage(k_lo, 0);
+  for (int t = 0; t < nch; ++t) {
+    const int cur = t & 1;
+    if (t + 1 < nch) {
+      stage(k_lo + (t + 1) * BK, cur ^ 1);
+      wait_vmcnt<NPER>();
+    } else {
+      wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    compute(As[cur], Bs[cur]);
+    __builtin_amdgcn_s_barrier();
+  }
+}
+
+// host side: DT -> element type. f receives a TypeTag<float> or
+// TypeTag<bf16>, so each launcher body is written once:
+//   dispatch_dt(dt, [&](auto tag) {
+//     using T = typename decltype(tag)::type; ... });
+template <typename T> struct TypeTag { using type = T; };
+template <typename F>
+static void dispatch_dt(DT dt, F&& f) {
+  if (dt == DT::F32) f(TypeTag<float>{});
+  else f(TypeTag<bf16>{});
+}
+
+// elements per 16-byte vector; glds / vector routes need K % this == 0
+static int vec_elems(DT dt) { return dt == DT::F32 ? 4 : 8; }
+
+// ---------------------------------------------------------------------------
+// NN / NT kernel: C[M,N] = act(A[M,K] @ B + bias) + resid
 //   TRANS_B = false: B is [K, N] row-major (staged transposed into LDS)
 //   TRANS_B = true:  B is [N, K] row-major (staged directly; C = A @ B^T)
 // ---------------------------------------------------------------------------
@@ -22,12 +194,10 @@ using namespace tile;
 template <typename T, bool TRANS_B, bool GLDS>
 __launch_bounds__(THREADS)
 __global__ void k_gemm(const T* __restrict__ A, const T* __restrict__ B,
-                       const float* __restrict__ bias_f32,
-                       const T* __restrict__ bias_t, T* __restrict__ C,
+                       const T* __restrict__ bias, T* __restrict__ C,
                        const T* __restrict__ zero16,
                        const T* __restrict__ resid, int M, int N, int K,
                        int act_kind) {
-  constexpr int V = 16 / sizeof(T);  // elems per 16B vector
   __shared__ alignas(16) T As[BM * BK];
   __shared__ alignas(16) T Bs[BN * BK];
 
@@ -36,107 +206,29 @@ __global__ void k_gemm(const T* __restrict__ A, const T* __restrict__ B,
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
 
-  using VecT = Pack16<T>;
-
   for (int k0 = 0; k0 < K; k0 += BK) {
-    if constexpr (GLDS) {
-      // K % V == 0 and A 16B-aligned guaranteed by the launcher
-      glds_stage_a<T>(As, wc, [&](int rl, int kk) -> const T* {
-        int gm = m0 + rl, gk = k0 + kk;
-        if (gm >= M || gk >= K) return zero16;
-        return &A[(int64_t)gm * K + gk];
-      });
-    } else {
-    // ---- stage A: [BM][BK], vectorized, zero-filled at edges ----
-#pragma unroll
-    for (int c = threadIdx.x; c < BM * (BK / V); c += THREADS) {
-      int row = c / (BK / V);
-      int kk = (c % (BK / V)) * V;
-      int gm = m0 + row, gk = k0 + kk;
-      VecT v = {};
-      if (gm < M) {
-        const T* src = &A[(int64_t)gm * K + gk];
-        if (gk + V <= K && aligned16(src)) {
-          v = *(const VecT*)src;
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j)
-            if (gk + j < K) v.e[j] = A[(int64_t)gm * K + gk + j];
-        }
-      }
-      *(VecT*)&As[lds_off<T>(row, kk)] = v;
-    }
-    }
-    // ---- stage B into Bs[n][k] ----
-    if constexpr (TRANS_B && GLDS) {
-      // B[N,K] rows are already the image rows: same DMA form as A
-      glds_stage<T, BN>(Bs, wc, [&](int rl, int kk) -> const T* {
-        int gn = n0 + rl, gk = k0 + kk;
-        if (gn >= N || gk >= K) return zero16;
-        return &B[(int64_t)gn * K + gk];
-      });
-    } else if constexpr (TRANS_B) {
-      // B[N,K]: rows are output columns; contiguous copy
-#pragma unroll
-      for (int c = threadIdx.x; c < BN * (BK / V); c += THREADS) {
-        int col = c / (BK / V);
-        int kk = (c % (BK / V)) * V;
-        int gn = n0 + col, gk = k0 + kk;
-        VecT v = {};
-        if (gn < N) {
-          const T* src = &B[(int64_t)gn * K + gk];
-          if (gk + V <= K && aligned16(src)) {
-            v = *(const VecT*)src;
-          } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j)
-              if (gk + j < K) v.e[j] = B[(int64_t)gn * K + gk + j];
-          }
-        }
-        *(VecT*)&Bs[lds_off<T>(col, kk)] = v;
-      }
-    } else {
-      // B[K,N]: load n-contiguous vectors, scatter-transpose into LDS
-#pragma unroll 1
-      for (int c = threadIdx.x; c < BK * (BN / V); c += THREADS) {
-        int kk = c / (BN / V);
-        int nn = (c % (BN / V)) * V;
-        int gk = k0 + kk, gn = n0 + nn;
-        VecT v = {};
-        if (gk < K) {
-          const T* src = &B[(int64_t)gk * N + gn];
-          if (gn + V <= N && aligned16(src)) {
-            v = *(const VecT*)src;
-          } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j)
-              if (gn + j < N) v.e[j] = B[(int64_t)gk * N + gn + j];
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-          Bs[lds_off<T>(nn + j, kk)] = v.e[j];
-      }
-    }
+    // A[M,K] and (TRANS_B) B[N,K] rows are already the image rows. GLDS:
+    // K % V == 0 and 16B-aligned A guaranteed by the launcher.
+    if constexpr (GLDS)
+      glds_stage_rows<T, BM>(As, wc, A, zero16, m0, M, K, k0, K);
+    else
+      stage_rows<T, BM>(As, A, m0, M, k0, K);
+    if constexpr (TRANS_B && GLDS)
+      glds_stage_rows<T, BN>(Bs, wc, B, zero16, n0, N, K, k0, K);
+    else if constexpr (TRANS_B)
+      stage_rows<T, BN>(Bs, B, n0, N, k0, K);
+    else  // B[K,N]: n-contiguous loads, scatter-transposed into Bs[n][k]
+      stage_transposed<T, BN>(Bs, B, N, k0, K, n0);
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
     __syncthreads();
   }
 
-  // ---- epilogue: bias + activation + residual + cast store ----
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < N) {
-      if (bias_f32) v += bias_f32[col];
-      if (bias_t) v += VecIO<T>::to_f32(bias_t[col]);
-      if (act_kind != ACT_LINEAR) v = act_apply(v, act_kind);
-      if (resid) v += VecIO<T>::to_f32(resid[(int64_t)row * N + col]);
-      C[(int64_t)row * N + col] = VecIO<T>::from_f32(v);
-    }
-  });
+  epilogue_store(wc, acc, C, m0, n0, M, N, {bias, resid, N, act_kind});
 }
 
 // ---------------------------------------------------------------------------
-// TN kernel: C[K,N] += A[M,K]^T @ B[M,N], fp32 atomic accumulate.
+// TN kernel: C[K,N] = A[M,K]^T @ B[M,N] into per-slice fp32 slabs.
 // Grid.z slices the M reduction (split-K in the GEMM sense) so small-output
 // wgrads still fill 256 CUs (SURVEY §7 hard part 1).
 // ---------------------------------------------------------------------------
@@ -145,7 +237,6 @@ template <typename T>
 __launch_bounds__(THREADS, 3)  // cap VGPRs: unconstrained allocation hit 221-256 VGPR = 1-2 waves/SIMD
 __global__ void k_gemm_tn(const T* __restrict__ A, const T* __restrict__ B,
                           float* __restrict__ C, int M, int N, int K) {
-  constexpr int V = 16 / sizeof(T);
   __shared__ alignas(16) T As[BM * BK];  // rows = K-dim, k = m-chunk
   __shared__ alignas(16) T Bs[BN * BK];
 
@@ -158,76 +249,25 @@ __global__ void k_gemm_tn(const T* __restrict__ A, const T* __restrict__ B,
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
 
-  using VecT = Pack16<T>;
-
   for (int k0 = m_begin; k0 < m_end; k0 += BK) {
-    // ---- stage A^T: load A[m][r..r+V] (contiguous), scatter to As[r][m] ----
-#pragma unroll 1  // full unroll quadruples live address state (spills)
-    for (int c = threadIdx.x; c < BK * (BM / V); c += THREADS) {
-      int mm = c / (BM / V);
-      int rr = (c % (BM / V)) * V;
-      int gm = k0 + mm;
-      int gr = r0 + rr;
-      VecT v = {};
-      if (gm < m_end) {
-        const T* src = &A[(int64_t)gm * K + gr];
-        if (gr + V <= K && aligned16(src)) {
-          v = *(const VecT*)src;
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j)
-            if (gr + j < K) v.e[j] = A[(int64_t)gm * K + gr + j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        As[lds_off<T>(rr + j, mm)] = v.e[j];
-    }
-    // ---- stage B[m][n] -> Bs[n][m] ----
-#pragma unroll 1
-    for (int c = threadIdx.x; c < BK * (BN / V); c += THREADS) {
-      int mm = c / (BN / V);
-      int nn = (c % (BN / V)) * V;
-      int gm = k0 + mm;
-      int gn = n0 + nn;
-      VecT v = {};
-      if (gm < m_end) {
-        const T* src = &B[(int64_t)gm * N + gn];
-        if (gn + V <= N && aligned16(src)) {
-          v = *(const VecT*)src;
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j)
-            if (gn + j < N) v.e[j] = B[(int64_t)gm * N + gn + j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        Bs[lds_off<T>(nn + j, mm)] = v.e[j];
-    }
+    stage_transposed<T, BM>(As, A, K, k0, m_end, r0);  // A[m][r] -> As[r][m]
+    stage_transposed<T, BN>(Bs, B, N, k0, m_end, n0);  // B[m][n] -> Bs[n][m]
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
     __syncthreads();
   }
 
-  // slab write: block z owns slab z of the fp32 workspace (C when z==1);
-  // a separate reduce pass sums slabs — deterministic, no atomic contention
-  float* out = C + (int64_t)blockIdx.z * K * N;
-  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
-    if (row < K && col < N) out[(int64_t)row * N + col] = v;
-  });
+  slab_store(wc, acc, C, r0, n0, K, N);
 }
 
-// double-buffered pure-glds NT gemm (see k_conv_fwd_db): A[M,K] and
-// B[N,K] rows are both k-contiguous, so the next chunk's LDS-DMAs overlap
-// the current chunk's MFMAs. Dispatched for K <= 3072 (2x LDS buffers cap
+// double-buffered pure-glds NT gemm (see k_conv_fwd_db and
+// nt_db_mainloop). Dispatched for K <= 3072 (2x LDS buffers cap
 // occupancy at 3 blocks/CU; long k-loops prefer the 6-block single-buffer
 // kernel).
 template <typename T>
 __launch_bounds__(THREADS)
 __global__ void k_gemm_nt_db(const T* __restrict__ A, const T* __restrict__ B,
-                             const float* __restrict__ bias_f32,
-                             const T* __restrict__ bias_t, T* __restrict__ C,
+                             const T* __restrict__ bias, T* __restrict__ C,
                              const T* __restrict__ zero16,
                              const T* __restrict__ resid, int M, int N, int K,
                              int act_kind) {
@@ -238,45 +278,12 @@ __global__ void k_gemm_nt_db(const T* __restrict__ A, const T* __restrict__ B,
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
 
-  auto stage = [&](int t, int which) {
-    int kk0 = t * BK;
-    glds_stage<T, BM>(As[which], wc, [&](int rl, int kk) -> const T* {
-      int gm = m0 + rl, gk = kk0 + kk;
-      if (gm >= M || gk >= K) return zero16;
-      return &A[(int64_t)gm * K + gk];
-    });
-    glds_stage<T, BN>(Bs[which], wc, [&](int rl, int kk) -> const T* {
-      int gn = n0 + rl, gk = kk0 + kk;
-      if (gn >= N || gk >= K) return zero16;
-      return &B[(int64_t)gn * K + gk];
-    });
-  };
-  constexpr int NPER = glds_count<T, BM>() + glds_count<T, BN>();
+  nt_db_mainloop(A, B, zero16, As, Bs, wc, m0, n0, M, N, K, 0, K,
+                 [&](const T* as, const T* bs) {
+                   mfma_compute_tile(as, bs, wc, acc);
+                 });
 
-  const int nch = (K + BK - 1) / BK;
-  stage(0, 0);
-  for (int t = 0; t < nch; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < nch) {
-      stage(t + 1, cur ^ 1);
-      wait_vmcnt<NPER>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    mfma_compute_tile(As[cur], Bs[cur], wc, acc);
-    __builtin_amdgcn_s_barrier();
-  }
-
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < N) {
-      if (bias_f32) v += bias_f32[col];
-      if (bias_t) v += VecIO<T>::to_f32(bias_t[col]);
-      if (act_kind != ACT_LINEAR) v = act_apply(v, act_kind);
-      if (resid) v += VecIO<T>::to_f32(resid[(int64_t)row * N + col]);
-      C[(int64_t)row * N + col] = VecIO<T>::from_f32(v);
-    }
-  });
+  epilogue_store(wc, acc, C, m0, n0, M, N, {bias, resid, N, act_kind});
 }
 
 // M=1 NT matvec (decode-path linears): one wave per output row, 16B loads
@@ -285,8 +292,8 @@ __global__ void k_gemm_nt_db(const T* __restrict__ A, const T* __restrict__ B,
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_gemv_nt(const T* __restrict__ x, const T* __restrict__ B,
-                          const float* __restrict__ bias_f32,
-                          const T* __restrict__ bias_t, T* __restrict__ y,
+                          const T* __restrict__ bias,
+                          const T* __restrict__ resid, T* __restrict__ y,
                           int N, int K, int act_kind) {
   constexpr int V = 16 / sizeof(T);
   using VecT = Pack16<T>;
@@ -311,20 +318,16 @@ __global__ void k_gemv_nt(const T* __restrict__ x, const T* __restrict__ B,
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
     acc += __shfl_xor(acc, off, 64);
-  if (lane == 0) {
-    if (bias_f32) acc += bias_f32[n];
-    if (bias_t) acc += VecIO<T>::to_f32(bias_t[n]);
-    if (act_kind != ACT_LINEAR) acc = act_apply(acc, act_kind);
-    y[n] = VecIO<T>::from_f32(acc);
-  }
+  if (lane == 0)
+    y[n] = VecIO<T>::from_f32(
+        Epilogue<T>{bias, resid, N, act_kind}(acc, 0, n));
 }
 
 // K-split NT gemm for huge-K underfilled shapes (the GPT-2 vocab-head
 // dgrad: dx[4096,768] = dy[4096,50264] @ W^T — 384 blocks and a 785-
 // chunk k-loop on the plain kernel, 313 TF). grid.z slices K; each
 // slice writes an fp32 slab, the split-K reduce (shared with wgrad)
-// sums and casts. Double-buffered glds staging (both operands' rows are
-// k-contiguous).
+// sums and casts. Same double-buffered main loop as k_gemm_nt_db.
 template <typename T>
 __launch_bounds__(THREADS)
 __global__ void k_gemm_nt_z(const T* __restrict__ A, const T* __restrict__ B,
@@ -335,47 +338,17 @@ __global__ void k_gemm_nt_z(const T* __restrict__ A, const T* __restrict__ B,
   __shared__ alignas(16) T Bs[2][BN * BK];
   const int m0 = blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
-  const int Z = gridDim.z;
-  const int k_lo = (int)(((int64_t)K * blockIdx.z / Z) / BK * BK);
-  const int k_hi = blockIdx.z + 1 == Z
-                       ? K
-                       : (int)(((int64_t)K * (blockIdx.z + 1) / Z) / BK * BK);
+  int k_lo, k_hi;
+  ksplit_range(K, k_lo, k_hi);
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
 
-  auto stage = [&](int kk0, int which) {
-    glds_stage<T, BM>(As[which], wc, [&](int rl, int kk) -> const T* {
-      int gm = m0 + rl, gk = kk0 + kk;
-      if (gm >= M || gk >= k_hi) return zero16;
-      return &A[(int64_t)gm * K + gk];
-    });
-    glds_stage<T, BN>(Bs[which], wc, [&](int rl, int kk) -> const T* {
-      int gn = n0 + rl, gk = kk0 + kk;
-      if (gn >= N || gk >= k_hi) return zero16;
-      return &B[(int64_t)gn * K + gk];
-    });
-  };
-  constexpr int NPER = glds_count<T, BM>() + glds_count<T, BN>();
+  nt_db_mainloop(A, B, zero16, As, Bs, wc, m0, n0, M, N, K, k_lo, k_hi,
+                 [&](const T* as, const T* bs) {
+                   mfma_compute_tile(as, bs, wc, acc);
+                 });
 
-  const int nch = (k_hi - k_lo + BK - 1) / BK;
-  stage(k_lo, 0);
-  for (int t = 0; t < nch; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < nch) {
-      stage(k_lo + (t + 1) * BK, cur ^ 1);
-      wait_vmcnt<NPER>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    mfma_compute_tile(As[cur], Bs[cur], wc, acc);
-    __builtin_amdgcn_s_barrier();
-  }
-
-  float* out = Cws + (int64_t)blockIdx.z * M * N;
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < N) out[(int64_t)row * N + col] = v;
-  });
+  slab_store(wc, acc, Cws, m0, n0, M, N);
 }
 
 // ---------------------------------------------------------------------------
@@ -383,12 +356,11 @@ __global__ void k_gemm_nt_z(const T* __restrict__ A, const T* __restrict__ B,
 // per SIMD to cover its ~17 cyc/SIMD single-wave issue floor, but
 // v_mfma_f32_32x32x16_bf16 sustains PEAK issue at ONE wave/SIMD
 // (MI355X_MICROARCH.md cycle table) and touches half the LDS bytes per
-// FLOP (A/B reuse 32 wide, not 16). Block tile 128x128 (2x2 waves of
-// 64x64, FM=FN=2 fragments of 32x32), BK=64, double-buffered glds
-// staging, optional K-split over blockIdx.z into fp32 slabs (finalized
-// by k_splitk_fin_ep with the bias/act/residual epilogue).
-namespace nt32 {
-constexpr int BM2 = 128, BN2 = 64, BK2 = 64;
+// FLOP (A/B reuse 32 wide, not 16). Same 128x64 block tile and BK=64 as
+// the 16x16 core (4 M-stacked waves of 32x64, two 32x32 fragments each),
+// the shared double-buffered glds main loop, optional K-split over
+// blockIdx.z into fp32 slabs (finalized by k_splitk_fin_ep with the
+// bias/act/residual epilogue).
 #ifndef GEMM_REMAP_GM
 #define GEMM_REMAP_GM 8
 #endif
@@ -398,32 +370,28 @@ constexpr int BM2 = 128, BN2 = 64, BK2 = 64;
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_gemm_nt32(const T* __restrict__ A, const T* __restrict__ B,
-                            const float* __restrict__ bias_f32,
-                            const T* __restrict__ bias_t, T* __restrict__ C,
+                            const T* __restrict__ bias, T* __restrict__ C,
                             float* __restrict__ Cws,
                             const T* __restrict__ zero16,
                             const T* __restrict__ resid, int M, int N, int K,
                             int act_kind) {
-  using namespace tile;
-  __shared__ alignas(16) T As[2][BM2 * BK2];
-  __shared__ alignas(16) T Bs[2][BN2 * BK2];
+  __shared__ alignas(16) T As[2][BM * BK];
+  __shared__ alignas(16) T Bs[2][BN * BK];
   int tm, tn;
   // grouped ordering pays only when the re-read streams exceed the
   // 256 MiB L3 (vocab-head-sized operands measured +9%; L3-resident
   // shapes were flat-to-negative)
   if ((int64_t)M * N + (int64_t)N * K > (int64_t)48 * 1024 * 1024)
-    tile::tile_remap<GEMM_REMAP_GM>(tm, tn);
+    tile_remap<GEMM_REMAP_GM>(tm, tn);
   else {
     tm = blockIdx.x;
     tn = blockIdx.y;
   }
-  const int m0 = tm * BM2;
-  const int n0 = tn * BN2;
+  const int m0 = tm * BM;
+  const int n0 = tn * BN;
   const int Z = gridDim.z;
-  const int k_lo = Z == 1 ? 0 : (int)(((int64_t)K * blockIdx.z / Z) / BK2 * BK2);
-  const int k_hi = (Z == 1 || blockIdx.z + 1 == Z)
-                       ? K
-                       : (int)(((int64_t)K * (blockIdx.z + 1) / Z) / BK2 * BK2);
+  int k_lo, k_hi;
+  ksplit_range(K, k_lo, k_hi);
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int wrow0 = wid * 32;   // 4 M-stacked waves: 32 rows x 64 cols each
@@ -431,72 +399,43 @@ __global__ void k_gemm_nt32(const T* __restrict__ A, const T* __restrict__ B,
 
   f32x16 acc[2] = {};
 
-  auto stage = [&](int kk0, int which) {
-    glds_stage<T, BM2>(As[which], wc, [&](int rl, int kk) -> const T* {
-      int gm = m0 + rl, gk = kk0 + kk;
-      if (gm >= M || gk >= k_hi) return zero16;
-      return &A[(int64_t)gm * K + gk];
-    });
-    glds_stage<T, BN2>(Bs[which], wc, [&](int rl, int kk) -> const T* {
-      int gn = n0 + rl, gk = kk0 + kk;
-      if (gn >= N || gk >= k_hi) return zero16;
-      return &B[(int64_t)gn * K + gk];
-    });
-  };
-  constexpr int NPER = glds_count<T, BM2>() + glds_count<T, BN2>();
-
-  const int nch = (k_hi - k_lo + BK2 - 1) / BK2;
-  stage(k_lo, 0);
-  for (int t = 0; t < nch; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < nch) {
-      stage(k_lo + (t + 1) * BK2, cur ^ 1);
-      wait_vmcnt<NPER>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    // a-frag: lane supplies row (lane&31), k (lane>>5)*8..+8
-    const int ar = lane & 31;
-    const int kh = (lane >> 5) * 8;
+  // a-frag: lane supplies row (lane&31), k (lane>>5)*8..+8
+  const int ar = lane & 31;
+  const int kh = (lane >> 5) * 8;
+  nt_db_mainloop(A, B, zero16, As, Bs, wc, m0, n0, M, N, K, k_lo, k_hi,
+                 [&](const T* as, const T* bs) {
 #pragma unroll
-    for (int ks = 0; ks < BK2 / 16; ++ks) {
+    for (int ks = 0; ks < BK / 16; ++ks) {
       const int kb = ks * 16 + kh;
       bf16x8 a, b[2];
-      a = *(const bf16x8*)&As[cur][lds_off<T>(wrow0 + ar, kb)];
+      a = *(const bf16x8*)&as[lds_off<T>(wrow0 + ar, kb)];
 #pragma unroll
       for (int fn = 0; fn < 2; ++fn)
-        b[fn] = *(const bf16x8*)&Bs[cur][lds_off<T>(fn * 32 + ar, kb)];
+        b[fn] = *(const bf16x8*)&bs[lds_off<T>(fn * 32 + ar, kb)];
 #pragma unroll
       for (int fn = 0; fn < 2; ++fn)
         acc[fn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
             a, b[fn], acc[fn], 0, 0, 0);
     }
-    __builtin_amdgcn_s_barrier();
-  }
+  });
 
-  // epilogue
+  const Epilogue<T> ep{bias, resid, N, act_kind};
   const int cc = lane & 31;
   const int r4 = (lane >> 5) * 4;
 #pragma unroll
-    for (int fn = 0; fn < 2; ++fn)
+  for (int fn = 0; fn < 2; ++fn)
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int row = m0 + wrow0 + (reg & 3) + 8 * (reg >> 2) + r4;
-        const int col = n0 + fn * 32 + cc;
-        if (row >= M || col >= N) continue;
-        float vv = acc[fn][reg];
-        if (Z > 1) {
-          Cws[(int64_t)blockIdx.z * M * N + (int64_t)row * N + col] = vv;
-        } else {
-          if (bias_f32) vv += bias_f32[col];
-          else if (bias_t) vv += VecIO<T>::to_f32(bias_t[col]);
-          if (resid) vv += VecIO<T>::to_f32(resid[(int64_t)row * N + col]);
-          C[(int64_t)row * N + col] = VecIO<T>::from_f32(act_apply(vv, act_kind));
-        }
-      }
+    for (int reg = 0; reg < 16; ++reg) {
+      const int row = m0 + wrow0 + (reg & 3) + 8 * (reg >> 2) + r4;
+      const int col = n0 + fn * 32 + cc;
+      if (row >= M || col >= N) continue;
+      const float vv = acc[fn][reg];
+      if (Z > 1)
+        Cws[(int64_t)blockIdx.z * M * N + (int64_t)row * N + col] = vv;
+      else
+        C[(int64_t)row * N + col] = VecIO<T>::from_f32(ep(vv, row, col));
+    }
 }
-}  // namespace nt32
 
 // split-K for moderately underfilled FORWARD NT shapes (e.g. the
 // transformer's [B*S, 768] projections: 384 blocks on 256 CUs ran at
@@ -505,25 +444,24 @@ __global__ void k_gemm_nt32(const T* __restrict__ A, const T* __restrict__ B,
 int gemm_nt_fsplits(DT dt, int M, int N, int K) {
   const int base = ceil_div(M, BM) * ceil_div(N, BN);
   if (base >= 768 || K < 4 * BK) return 1;
-  const bool g = dt == DT::F32 ? K % 4 == 0 : K % 8 == 0;
-  if (!g) return 1;
+  if (K % vec_elems(dt) != 0) return 1;
   return std::min(ceil_div(768, base), K / (2 * BK));
 }
 
-// fused split-K finalize: fold the Z fp32 slabs, add bias / residual,
-// apply the activation, cast to T (the bias/act/resid epilogue the
-// direct kernels do, relocated here for the z-split route)
+// fused split-K finalize: fold the Z fp32 slabs, then the same Epilogue
+// the direct kernels apply (relocated here for the z-split routes), cast
+// to T
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_splitk_fin_ep(const float4* __restrict__ ws,
-                                const float* __restrict__ bias_f32,
-                                const T* __restrict__ bias_t,
+                                const T* __restrict__ bias,
                                 const T* __restrict__ resid,
                                 T* __restrict__ out, int z, int N,
                                 int64_t n4, int act_kind) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   struct alignas(4 * sizeof(T)) T4 { T e[4]; };
+  const Epilogue<T> ep{bias, resid, N, act_kind};
   for (; i < n4; i += stride) {
     float4 a{0.0f, 0.0f, 0.0f, 0.0f};
     for (int sl = 0; sl < z; ++sl) {
@@ -534,93 +472,81 @@ __global__ void k_splitk_fin_ep(const float4* __restrict__ ws,
     const int col0 = (int)((i * 4) % N);
     T4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (bias_f32) r[j] += bias_f32[col0 + j];
-      else if (bias_t) r[j] += VecIO<T>::to_f32(bias_t[col0 + j]);
-      if (resid) r[j] += VecIO<T>::to_f32(resid[i * 4 + j]);
-      o.e[j] = VecIO<T>::from_f32(act_apply(r[j], act_kind));
-    }
+    for (int j = 0; j < 4; ++j)
+      o.e[j] = VecIO<T>::from_f32(ep.at(r[j], col0 + j, i * 4 + j));
     ((T4*)out)[i] = o;
   }
 }
 
-void gemm_nt_zf_launch(DT dt, const void* a, const void* b, float* ws,
-                       const void* bias_f32_or_t, const void* resid, void* c,
-                       int z, const void* zero16, int M, int N, int K,
-                       int act_kind, hipStream_t s) {
-  dim3 grid(ceil_div(M, BM), ceil_div(N, BN), z);
-  const int64_t n4 = (int64_t)M * N / 4;  // N % 4 == 0 enforced by caller
+// finalize launch shared by both split-K forward routes (N % 4 == 0
+// enforced by the callers)
+template <typename T>
+static void splitk_fin_ep_launch(const float* ws, const void* bias,
+                                 const void* resid, void* c, int z, int M,
+                                 int N, int act_kind, hipStream_t s) {
+  const int64_t n4 = (int64_t)M * N / 4;
   int blocks = (int)std::min<int64_t>((n4 + 255) / 256, (int64_t)2048);
-  if (dt == DT::F32) {
-    hipLaunchKernelGGL(k_gemm_nt_z<float>, grid, dim3(THREADS), 0, s,
-                       (const float*)a, (const float*)b, ws,
-                       (const float*)zero16, M, N, K);
-    hipLaunchKernelGGL(k_splitk_fin_ep<float>, dim3(blocks), dim3(256), 0, s,
-                       (const float4*)ws, (const float*)bias_f32_or_t,
-                       (const float*)nullptr, (const float*)resid, (float*)c,
-                       z, N, n4, act_kind);
-  } else {
-    hipLaunchKernelGGL(k_gemm_nt_z<bf16>, grid, dim3(THREADS), 0, s,
-                       (const bf16*)a, (const bf16*)b, ws,
-                       (const bf16*)zero16, M, N, K);
-    hipLaunchKernelGGL(k_splitk_fin_ep<bf16>, dim3(blocks), dim3(256), 0, s,
-                       (const float4*)ws, (const float*)nullptr,
-                       (const bf16*)bias_f32_or_t, (const bf16*)resid,
-                       (bf16*)c, z, N, n4, act_kind);
-  }
+  hipLaunchKernelGGL(k_splitk_fin_ep<T>, dim3(blocks), dim3(256), 0, s,
+                     (const float4*)ws, (const T*)bias, (const T*)resid,
+                     (T*)c, z, N, n4, act_kind);
+}
+
+template <typename T>
+static void gemm_nt_z_kernel_launch(const void* a, const void* b, float* ws,
+                                    int z, const void* zero16, int M, int N,
+                                    int K, hipStream_t s) {
+  dim3 grid(ceil_div(M, BM), ceil_div(N, BN), z);
+  hipLaunchKernelGGL(k_gemm_nt_z<T>, grid, dim3(THREADS), 0, s, (const T*)a,
+                     (const T*)b, ws, (const T*)zero16, M, N, K);
+}
+
+void gemm_nt_zf_launch(DT dt, const void* a, const void* b, float* ws,
+                       const void* bias, const void* resid, void* c, int z,
+                       const void* zero16, int M, int N, int K, int act_kind,
+                       hipStream_t s) {
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    gemm_nt_z_kernel_launch<T>(a, b, ws, z, zero16, M, N, K, s);
+    splitk_fin_ep_launch<T>(ws, bias, resid, c, z, M, N, act_kind, s);
+  });
 }
 
 // K-splits for the 32-wide NT kernel: fill to ~2 blocks/CU (its LDS
 // footprint caps residency at 2)
 int gemm_nt32_zsplits(int M, int N, int K) {
-  using namespace nt32;
-  const int base = ceil_div(M, BM2) * ceil_div(N, BN2);
-  if (base >= 512 || K < 4 * BK2) return 1;
+  const int base = ceil_div(M, BM) * ceil_div(N, BN);
+  if (base >= 512 || K < 4 * BK) return 1;
   if (K % 8 != 0) return 1;
-  return std::min(ceil_div(512, base), K / (2 * BK2));
+  return std::min(ceil_div(512, base), K / (2 * BK));
 }
 
 void gemm_nt32_launch(const void* a, const void* b, float* ws,
-                      const void* bias_f32, const void* bias_t,
-                      const void* resid, void* c, int z, const void* zero16,
-                      int M, int N, int K, int act_kind, hipStream_t s) {
-  using namespace nt32;
-  dim3 grid(ceil_div(M, BM2), ceil_div(N, BN2), z);
+                      const void* bias, const void* resid, void* c, int z,
+                      const void* zero16, int M, int N, int K, int act_kind,
+                      hipStream_t s) {
+  dim3 grid(ceil_div(M, BM), ceil_div(N, BN), z);
   hipLaunchKernelGGL(k_gemm_nt32<bf16>, grid, dim3(256), 0, s, (const bf16*)a,
-                     (const bf16*)b, (const float*)bias_f32,
-                     (const bf16*)bias_t, (bf16*)c, ws, (const bf16*)zero16,
-                     (const bf16*)resid, M, N, K, act_kind);
-  if (z > 1) {
-    const int64_t n4 = (int64_t)M * N / 4;
-    int blocks = (int)std::min<int64_t>((n4 + 255) / 256, (int64_t)2048);
-    hipLaunchKernelGGL(k_splitk_fin_ep<bf16>, dim3(blocks), dim3(256), 0, s,
-                       (const float4*)ws, (const float*)bias_f32,
-                       (const bf16*)bias_t, (const bf16*)resid, (bf16*)c, z,
-                       N, n4, act_kind);
-  }
+                     (const bf16*)b, (const bf16*)bias, (bf16*)c, ws,
+                     (const bf16*)zero16, (const bf16*)resid, M, N, K,
+                     act_kind);
+  if (z > 1)
+    splitk_fin_ep_launch<bf16>(ws, bias, resid, c, z, M, N, act_kind, s);
 }
-
 
 int gemm_nt_zsplits(DT dt, int M, int N, int K) {
   const int base = ceil_div(M, BM) * ceil_div(N, BN);
   if (base >= 768 || K < 4 * BK) return 1;
-  const bool g = dt == DT::F32 ? K % 4 == 0 : K % 8 == 0;
-  if (!g) return 1;
+  if (K % vec_elems(dt) != 0) return 1;
   return std::min(ceil_div(K, 4 * BK), ceil_div(1024, base));
 }
 
 void gemm_nt_z_launch(DT dt, const void* a, const void* b, float* ws,
                       void* c_out, DT out_dt, int z, const void* zero16,
                       int M, int N, int K, hipStream_t s) {
-  dim3 grid(ceil_div(M, BM), ceil_div(N, BN), z);
-  if (dt == DT::F32)
-    hipLaunchKernelGGL(k_gemm_nt_z<float>, grid, dim3(THREADS), 0, s,
-                       (const float*)a, (const float*)b, ws,
-                       (const float*)zero16, M, N, K);
-  else
-    hipLaunchKernelGGL(k_gemm_nt_z<bf16>, grid, dim3(THREADS), 0, s,
-                       (const bf16*)a, (const bf16*)b, ws,
-                       (const bf16*)zero16, M, N, K);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    gemm_nt_z_kernel_launch<T>(a, b, ws, z, zero16, M, N, K, s);
+  });
   splitk_reduce_launch(ws, c_out, out_dt, z, (int64_t)M * N, s);
 }
 
@@ -630,13 +556,10 @@ void gemm_nt_z_launch(DT dt, const void* a, const void* b, float* ws,
 // 48-deep serial slab reduce on 3 blocks); this is one latency-bound
 // pass (~2-3us). Blocks own 64 n-columns; the 4 thread-rows split K and
 // fold through LDS. K <= GEMV1_MAX_K (x LDS cache); larger K falls back.
-constexpr int GEMV1_MAX_K = 8192;
-
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_gemv_nn1(const T* __restrict__ x, const T* __restrict__ B,
-                           const float* __restrict__ bias_f32,
-                           const T* __restrict__ bias_t,
+                           const T* __restrict__ bias,
                            const T* __restrict__ res, T* __restrict__ y,
                            float* __restrict__ part,
                            const float* __restrict__ ln_g,
@@ -709,11 +632,7 @@ __global__ void k_gemv_nn1(const T* __restrict__ x, const T* __restrict__ B,
       part[(int64_t)blockIdx.y * N + n] = a;
       return;
     }
-    if (bias_f32) a += bias_f32[n];
-    if (bias_t) a += VecIO<T>::to_f32(bias_t[n]);
-    if (act_kind != ACT_LINEAR) a = act_apply(a, act_kind);
-    if (res) a += VecIO<T>::to_f32(res[n]);
-    y[n] = VecIO<T>::from_f32(a);
+    y[n] = VecIO<T>::from_f32(Epilogue<T>{bias, res, N, act_kind}(a, 0, n));
   }
 }
 
@@ -721,8 +640,7 @@ __global__ void k_gemv_nn1(const T* __restrict__ x, const T* __restrict__ B,
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_gemv_fin2(const float* __restrict__ part,
-                            const float* __restrict__ bias_f32,
-                            const T* __restrict__ bias_t,
+                            const T* __restrict__ bias,
                             const T* __restrict__ res, T* __restrict__ y,
                             int N, int nsplit, int act_kind) {
   const int n = blockIdx.x * 256 + threadIdx.x;
@@ -736,12 +654,8 @@ __global__ void k_gemv_fin2(const float* __restrict__ part,
     a3 += part[(int64_t)(s + 3) * N + n];
   }
   for (; s < nsplit; ++s) a0 += part[(int64_t)s * N + n];
-  float a = (a0 + a1) + (a2 + a3);
-  if (bias_f32) a += bias_f32[n];
-  if (bias_t) a += VecIO<T>::to_f32(bias_t[n]);
-  if (act_kind != ACT_LINEAR) a = act_apply(a, act_kind);
-  if (res) a += VecIO<T>::to_f32(res[n]);
-  y[n] = VecIO<T>::from_f32(a);
+  const float a = (a0 + a1) + (a2 + a3);
+  y[n] = VecIO<T>::from_f32(Epilogue<T>{bias, res, N, act_kind}(a, 0, n));
 }
 
 int gemv_nn1_nsplit(int N, int K) {
@@ -758,27 +672,17 @@ void gemv_nn1_launch(DT dt, const void* x, const void* b, const void* bias,
                      int K, int act_kind, hipStream_t s) {
   dim3 g(ceil_div(N, 64), nsplit);
   dim3 fg(ceil_div(N, 256));
-  if (dt == DT::F32) {
-    hipLaunchKernelGGL(k_gemv_nn1<float>, g, dim3(256), 0, s,
-                       (const float*)x, (const float*)b, (const float*)bias,
-                       (const float*)nullptr, (const float*)res, (float*)y,
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(k_gemv_nn1<T>, g, dim3(256), 0, s, (const T*)x,
+                       (const T*)b, (const T*)bias, (const T*)res, (T*)y,
                        nsplit > 1 ? part : nullptr, ln_g, ln_b, ln_eps, N, K,
                        act_kind);
     if (nsplit > 1)
-      hipLaunchKernelGGL(k_gemv_fin2<float>, fg, dim3(256), 0, s, part,
-                         (const float*)bias, (const float*)nullptr,
-                         (const float*)res, (float*)y, N, nsplit, act_kind);
-  } else {
-    hipLaunchKernelGGL(k_gemv_nn1<bf16>, g, dim3(256), 0, s, (const bf16*)x,
-                       (const bf16*)b, (const float*)nullptr,
-                       (const bf16*)bias, (const bf16*)res, (bf16*)y,
-                       nsplit > 1 ? part : nullptr, ln_g, ln_b, ln_eps, N, K,
-                       act_kind);
-    if (nsplit > 1)
-      hipLaunchKernelGGL(k_gemv_fin2<bf16>, fg, dim3(256), 0, s, part,
-                         (const float*)nullptr, (const bf16*)bias,
-                         (const bf16*)res, (bf16*)y, N, nsplit, act_kind);
-  }
+      hipLaunchKernelGGL(k_gemv_fin2<T>, fg, dim3(256), 0, s, part,
+                         (const T*)bias, (const T*)res, (T*)y, N, nsplit,
+                         act_kind);
+  });
 }
 
 // Legacy two-kernel K-split matvec (kept for K > GEMV1_MAX_K): fp32
@@ -805,17 +709,14 @@ __global__ void k_gemv_nn_part(const T* __restrict__ x, const T* __restrict__ B,
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_gemv_nn_fin(const float* __restrict__ ws,
-                              const float* __restrict__ bias_f32,
-                              const T* __restrict__ bias_t, T* __restrict__ y,
+                              const T* __restrict__ bias, T* __restrict__ y,
                               int N, int KS, int act_kind) {
   int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   float a = 0.0f;
   for (int s = 0; s < KS; ++s) a += ws[(int64_t)s * N + n];
-  if (bias_f32) a += bias_f32[n];
-  if (bias_t) a += VecIO<T>::to_f32(bias_t[n]);
-  if (act_kind != ACT_LINEAR) a = act_apply(a, act_kind);
-  y[n] = VecIO<T>::from_f32(a);
+  // no residual on this route (the binding rejects it)
+  y[n] = VecIO<T>::from_f32(Epilogue<T>{bias, nullptr, N, act_kind}(a, 0, n));
 }
 
 // vector-guaranteed TN gemm (K%V==0, N%V==0, aligned): 3-phase staging --
@@ -911,10 +812,7 @@ __global__ void k_gemm_tn_vec(const T* __restrict__ A, const T* __restrict__ B,
     __syncthreads();
   }
 
-  float* out = C + (int64_t)blockIdx.z * K * N;
-  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
-    if (row < K && col < N) out[(int64_t)row * N + col] = v;
-  });
+  slab_store(wc, acc, C, r0, n0, K, N);
 }
 
 template <typename OUT>
@@ -1024,33 +922,22 @@ static void splitk_fold_launch(const float4* ws, OUT* out, int z, int64_t n4,
 
 void splitk_reduce_launch(const float* ws, void* out, DT out_dt, int z,
                           int64_t n, hipStream_t s) {
-  if ((n & 3) == 0 && n < 4 * 32768 && z >= 8) {
-    // small output x deep z: parallelize over z (see k_splitk_fold)
-    int64_t n4 = n >> 2;
-    if (out_dt == DT::F32)
-      splitk_fold_launch((const float4*)ws, (float*)out, z, n4, s);
-    else
-      splitk_fold_launch((const float4*)ws, (bf16*)out, z, n4, s);
-    return;
-  }
-  if ((n & 3) == 0) {
-    int64_t n4 = n >> 2;
-    int blocks = (int)std::min<int64_t>((n4 + 255) / 256, (int64_t)2048);
-    if (out_dt == DT::F32)
-      hipLaunchKernelGGL(k_splitk_reduce4<float>, dim3(blocks), dim3(256), 0,
-                         s, (const float4*)ws, (float*)out, z, n4);
-    else
-      hipLaunchKernelGGL(k_splitk_reduce4<bf16>, dim3(blocks), dim3(256), 0,
-                         s, (const float4*)ws, (bf16*)out, z, n4);
-    return;
-  }
-  int blocks = (int)std::min<int64_t>((n + 255) / 256, (int64_t)2048);
-  if (out_dt == DT::F32)
-    hipLaunchKernelGGL(k_splitk_reduce<float>, dim3(blocks), dim3(256), 0, s,
-                       ws, (float*)out, z, n);
-  else
-    hipLaunchKernelGGL(k_splitk_reduce<bf16>, dim3(blocks), dim3(256), 0, s,
-                       ws, (bf16*)out, z, n);
+  dispatch_dt(out_dt, [&](auto tag) {
+    using OUT = typename decltype(tag)::type;
+    if ((n & 3) == 0 && n < 4 * 32768 && z >= 8) {
+      // small output x deep z: parallelize over z (see k_splitk_fold)
+      splitk_fold_launch((const float4*)ws, (OUT*)out, z, n >> 2, s);
+    } else if ((n & 3) == 0) {
+      int64_t n4 = n >> 2;
+      int blocks = (int)std::min<int64_t>((n4 + 255) / 256, (int64_t)2048);
+      hipLaunchKernelGGL(k_splitk_reduce4<OUT>, dim3(blocks), dim3(256), 0, s,
+                         (const float4*)ws, (OUT*)out, z, n4);
+    } else {
+      int blocks = (int)std::min<int64_t>((n + 255) / 256, (int64_t)2048);
+      hipLaunchKernelGGL(k_splitk_reduce<OUT>, dim3(blocks), dim3(256), 0, s,
+                         ws, (OUT*)out, z, n);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1060,56 +947,30 @@ void splitk_reduce_launch(const float* ws, void* out, DT out_dt, int z,
 void gemm_launch(DT dt, const void* a, const void* b, const void* bias,
                  void* c, const void* zero16, const void* resid, int M, int N,
                  int K, bool trans_b, int act_kind, hipStream_t s) {
-  if (M == 1 && trans_b) {  // decode-path matvec
-    dim3 gg(ceil_div(N, 4));
-    if (dt == DT::F32)
-      hipLaunchKernelGGL(k_gemv_nt<float>, gg, dim3(256), 0, s,
-                         (const float*)a, (const float*)b, (const float*)bias,
-                         (const float*)nullptr, (float*)c, N, K, act_kind);
-    else
-      hipLaunchKernelGGL(k_gemv_nt<bf16>, gg, dim3(256), 0, s, (const bf16*)a,
-                         (const bf16*)b, (const float*)nullptr,
-                         (const bf16*)bias, (bf16*)c, N, K, act_kind);
-    return;
-  }
-  dim3 grid(ceil_div(M, BM), ceil_div(N, BN));
-  dim3 blk(THREADS);
-  if (dt == DT::F32) {
-    bool g = K % 4 == 0 && (((uintptr_t)a & 15) == 0);
-    if (trans_b && g && K <= 3072 && (((uintptr_t)b & 15) == 0)) {
-      hipLaunchKernelGGL(k_gemm_nt_db<float>, grid, blk, 0, s,
-                         (const float*)a, (const float*)b, (const float*)bias,
-                         (const float*)nullptr, (float*)c,
-                         (const float*)zero16, (const float*)resid, M, N, K,
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const T* A = (const T*)a;
+    const T* B = (const T*)b;
+    if (M == 1 && trans_b) {  // decode-path matvec
+      hipLaunchKernelGGL(k_gemv_nt<T>, dim3(ceil_div(N, 4)), dim3(256), 0, s,
+                         A, B, (const T*)bias, (const T*)resid, (T*)c, N, K,
                          act_kind);
       return;
     }
-    auto kern = trans_b ? (g ? k_gemm<float, true, true>
-                             : k_gemm<float, true, false>)
-                        : (g ? k_gemm<float, false, true>
-                             : k_gemm<float, false, false>);
-    hipLaunchKernelGGL(kern, grid, blk, 0, s, (const float*)a, (const float*)b,
-                       (const float*)bias, (const float*)nullptr, (float*)c,
-                       (const float*)zero16, (const float*)resid, M, N, K,
-                       act_kind);
-  } else {
-    bool g = K % 8 == 0 && (((uintptr_t)a & 15) == 0);
-    if (trans_b && g && K <= 3072 && (((uintptr_t)b & 15) == 0)) {
-      hipLaunchKernelGGL(k_gemm_nt_db<bf16>, grid, blk, 0, s, (const bf16*)a,
-                         (const bf16*)b, (const float*)nullptr,
-                         (const bf16*)bias, (bf16*)c, (const bf16*)zero16,
-                         (const bf16*)resid, M, N, K, act_kind);
-      return;
-    }
-    auto kern = trans_b ? (g ? k_gemm<bf16, true, true>
-                             : k_gemm<bf16, true, false>)
-                        : (g ? k_gemm<bf16, false, true>
-                             : k_gemm<bf16, false, false>);
-    hipLaunchKernelGGL(kern, grid, blk, 0, s, (const bf16*)a, (const bf16*)b,
-                       (const float*)nullptr, (const bf16*)bias, (bf16*)c,
-                       (const bf16*)zero16, (const bf16*)resid, M, N, K,
-                       act_kind);
-  }
+    dim3 grid(ceil_div(M, BM), ceil_div(N, BN));
+    const bool g = K % vec_elems(dt) == 0 && ptr_aligned16(a);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, A, B,
+                         (const T*)bias, (T*)c, (const T*)zero16,
+                         (const T*)resid, M, N, K, act_kind);
+    };
+    if (trans_b && g && K <= 3072 && ptr_aligned16(b))
+      launch(k_gemm_nt_db<T>);
+    else if (trans_b)
+      launch(g ? k_gemm<T, true, true> : k_gemm<T, true, false>);
+    else
+      launch(g ? k_gemm<T, false, true> : k_gemm<T, false, false>);
+  });
 }
 
 int gemv_nn_ksplits(int N, int K) {
@@ -1124,19 +985,13 @@ void gemv_nn_launch(DT dt, const void* x, const void* b, const void* bias,
                     hipStream_t s) {
   dim3 pg(ceil_div(N, 256), ks);
   dim3 fg(ceil_div(N, 256));
-  if (dt == DT::F32) {
-    hipLaunchKernelGGL(k_gemv_nn_part<float>, pg, dim3(256), 0, s,
-                       (const float*)x, (const float*)b, ws, N, K);
-    hipLaunchKernelGGL(k_gemv_nn_fin<float>, fg, dim3(256), 0, s, ws,
-                       (const float*)bias, (const float*)nullptr, (float*)y, N,
-                       ks, act_kind);
-  } else {
-    hipLaunchKernelGGL(k_gemv_nn_part<bf16>, pg, dim3(256), 0, s,
-                       (const bf16*)x, (const bf16*)b, ws, N, K);
-    hipLaunchKernelGGL(k_gemv_nn_fin<bf16>, fg, dim3(256), 0, s, ws,
-                       (const float*)nullptr, (const bf16*)bias, (bf16*)y, N,
-                       ks, act_kind);
-  }
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(k_gemv_nn_part<T>, pg, dim3(256), 0, s, (const T*)x,
+                       (const T*)b, ws, N, K);
+    hipLaunchKernelGGL(k_gemv_nn_fin<T>, fg, dim3(256), 0, s, ws,
+                       (const T*)bias, (T*)y, N, ks, act_kind);
+  });
 }
 
 int gemm_tn_zsplits(int M, int N, int K) {
@@ -1152,25 +1007,19 @@ void gemm_tn_launch(DT dt, const void* a, const void* b, void* c_out,
   dim3 grid(ceil_div(K, BM), ceil_div(N, BN), z);
   bool direct = z == 1 && out_dt == DT::F32;
   float* target = direct ? (float*)c_out : ws;
-  if (dt == DT::F32) {
-    if (K % 4 == 0 && N % 4 == 0 && (((uintptr_t)a & 15) == 0) &&
-        (((uintptr_t)b & 15) == 0))
-      hipLaunchKernelGGL(k_gemm_tn_vec<float>, grid, dim3(THREADS), 0, s,
-                         (const float*)a, (const float*)b, target,
-                         (const float*)zero16, M, N, K);
+  const int V = vec_elems(dt);
+  const bool vec = K % V == 0 && N % V == 0 && ptr_aligned16(a) &&
+                   ptr_aligned16(b);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (vec)
+      hipLaunchKernelGGL(k_gemm_tn_vec<T>, grid, dim3(THREADS), 0, s,
+                         (const T*)a, (const T*)b, target, (const T*)zero16,
+                         M, N, K);
     else
-      hipLaunchKernelGGL(k_gemm_tn<float>, grid, dim3(THREADS), 0, s,
-                         (const float*)a, (const float*)b, target, M, N, K);
-  } else {
-    if (K % 8 == 0 && N % 8 == 0 && (((uintptr_t)a & 15) == 0) &&
-        (((uintptr_t)b & 15) == 0))
-      hipLaunchKernelGGL(k_gemm_tn_vec<bf16>, grid, dim3(THREADS), 0, s,
-                         (const bf16*)a, (const bf16*)b, target,
-                         (const bf16*)zero16, M, N, K);
-    else
-      hipLaunchKernelGGL(k_gemm_tn<bf16>, grid, dim3(THREADS), 0, s,
-                         (const bf16*)a, (const bf16*)b, target, M, N, K);
-  }
+      hipLaunchKernelGGL(k_gemm_tn<T>, grid, dim3(THREADS), 0, s, (const T*)a,
+                         (const T*)b, target, M, N, K);
+  });
   if (!direct)
     splitk_reduce_launch(ws, c_out, out_dt, z, (int64_t)K * N, s);
 }

@@ -10,6 +10,9 @@ namespace tnn {
 
 enum class DT { F32, BF16 };
 
+// host-side check that a device pointer can take 16-byte vector access
+inline bool ptr_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // ---- elementwise.hip -------------------------------------------------------
 void act_fwd_launch(DT dt, const void* x, void* y, int64_t n, int kind,
                     hipStream_t s);
@@ -44,7 +47,8 @@ void gemv_nn1_launch(DT dt, const void* x, const void* b, const void* bias,
                      const void* res, void* y, float* part, int nsplit,
                      const float* ln_g, const float* ln_b, float ln_eps, int N,
                      int K, int act_kind, hipStream_t s);
-constexpr int GEMV1_MAX_K_DECL = 8192;
+// largest K of the single-launch M=1 matvec (its fp32 x cache in LDS)
+constexpr int GEMV1_MAX_K = 8192;
 void gemv_nn_launch(DT dt, const void* x, const void* b, const void* bias,
                     void* y, float* ws, int ks, int N, int K, int act_kind,
                     hipStream_t s);
@@ -52,13 +56,13 @@ int gemm_nt_zsplits(DT dt, int M, int N, int K);
 int gemm_nt_fsplits(DT dt, int M, int N, int K);
 int gemm_nt32_zsplits(int M, int N, int K);
 void gemm_nt32_launch(const void* a, const void* b, float* ws,
-                      const void* bias_f32, const void* bias_t,
-                      const void* resid, void* c, int z, const void* zero16,
-                      int M, int N, int K, int act_kind, hipStream_t s);
+                      const void* bias, const void* resid, void* c, int z,
+                      const void* zero16, int M, int N, int K, int act_kind,
+                      hipStream_t s);
 void gemm_nt_zf_launch(DT dt, const void* a, const void* b, float* ws,
-                       const void* bias_f32_or_t, const void* resid, void* c,
-                       int z, const void* zero16, int M, int N, int K,
-                       int act_kind, hipStream_t s);
+                       const void* bias, const void* resid, void* c, int z,
+                       const void* zero16, int M, int N, int K, int act_kind,
+                       hipStream_t s);
 void gemm_nt_z_launch(DT dt, const void* a, const void* b, float* ws,
                       void* c_out, DT out_dt, int z, const void* zero16,
                       int M, int N, int K, hipStream_t s);

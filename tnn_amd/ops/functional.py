@@ -309,8 +309,9 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, act, residual=None):
         ext = _C.ext()
-        assert residual is None or act == "linear", \
-            "fused residual requires act='linear' (relu mask would include it)"
+        # every GEMM route computes act(xw + b) + residual, so forward may
+        # fuse any pair; linear() refuses relu + residual with grad enabled
+        # and backward refuses to replay a mask from such a y
         y = ext.gemm(x, w, bias, ACT_KINDS[act], residual)
         ctx.save_for_backward(x, w, y if act != "linear" else None)
         ctx.act = act
@@ -325,6 +326,8 @@ class _Linear(torch.autograd.Function):
         dy = dy.contiguous()
         dres = dy if ctx.has_res else None
         if ctx.act == "relu":
+            assert not ctx.has_res, \
+                "fused residual requires act='linear' (relu mask would include it)"
             dy = ext.relu_bwd_mask(dy, y)
         elif ctx.act != "linear":
             raise NotImplementedError(f"fused act bwd for {ctx.act}")
@@ -412,7 +415,9 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
            ln: Optional[tuple] = None) -> torch.Tensor:
     """y = act(ln?(x) @ w + bias) [+ residual]; x ``[..., K]``, w ``[K, N]``
     row-major. ``residual`` (shape of y) fuses the add into the GEMM
-    epilogue on GPU (act must be 'linear'). ``ln=(gamma, beta, eps)``
+    epilogue on GPU (under no_grad together with any activation; with
+    grad enabled act='relu' plus a residual is an error, other
+    activations run unfused). ``ln=(gamma, beta, eps)``
     fuses a LayerNorm of x into the decode GEMV's staging (M=1,
     inference only)."""
     lead = x.shape[:-1]
@@ -437,6 +442,11 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
                         or not torch.is_grad_enabled()) else "linear"
         r2 = (residual.reshape(-1, residual.shape[-1]).contiguous()
               if residual is not None else None)
+        # with grad enabled a fused relu + residual stays an error: the
+        # backward's mask replay reads y, which would include the residual
+        assert (r2 is None or fused != "relu"
+                or not torch.is_grad_enabled()), \
+            "fused residual requires act='linear' when grad is enabled"
         y = _Linear.apply(x2.contiguous(), w.contiguous(),
                           None if bias is None else bias.contiguous(), fused,
                           r2 if fused == act else None)
