@@ -67,6 +67,14 @@ def bench_conv(dtype=torch.bfloat16):
             dy, w, H, W, S, S, P, P)), fl)
         report(f"conv_wgrad", f"{name} mb{N}", timeit(lambda: ext.conv2d_wgrad(
             x, dy, KS, KS, S, S, P, P, False)), fl)
+        # weight + bias gradient: the fused binding vs the pair it replaces
+        report(f"conv_wgrad+bias", f"{name} mb{N}", timeit(
+            lambda: ext.conv2d_wgrad_bias(x, dy, KS, KS, S, S, P, P, False)),
+            fl)
+        dy2 = dy.reshape(-1, Co)
+        report(f"conv_wgrad,colsum", f"{name} mb{N}", timeit(
+            lambda: (ext.conv2d_wgrad(x, dy, KS, KS, S, S, P, P, False),
+                     ext.colsum(dy2))), fl)
 
 
 def bench_bn(dtype=torch.bfloat16):

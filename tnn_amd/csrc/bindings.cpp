@@ -446,28 +446,52 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H,
   return dx;
 }
 
-at::Tensor conv2d_wgrad(const at::Tensor& x, const at::Tensor& dy, int64_t KH,
-                        int64_t KW, int64_t sh, int64_t sw, int64_t ph,
-                        int64_t pw, bool out_in_dt) {
+// returns [KH*KW*Cin (+1 with bias), Cout]: dw rows, then the bias-gradient row
+static at::Tensor conv2d_wgrad_rows(const at::Tensor& x, const at::Tensor& dy,
+                                    int64_t KH, int64_t KW, int64_t sh,
+                                    int64_t sw, int64_t ph, int64_t pw,
+                                    bool out_in_dt, bool bias) {
   CHECK_IN(x);
   CHECK_IN(dy);
   auto cs = conv_shape(x, x.size(3), dy.size(3), KH, KW, sh, sw, ph, pw);
   TORCH_CHECK(dy.size(1) == cs.OH && dy.size(2) == cs.OW, "wgrad shape");
   DT out_dt = out_in_dt ? dt_of(x) : DT::F32;
-  auto dw = at::empty({KH, KW, cs.Cin, cs.Cout},
-                      out_dt == DT::F32 ? x.options().dtype(at::kFloat)
-                                        : x.options());
+  const int64_t rows = KH * KW * cs.Cin + (bias ? 1 : 0);
+  auto out = at::empty({rows, (int64_t)cs.Cout},
+                       out_dt == DT::F32 ? x.options().dtype(at::kFloat)
+                                         : x.options());
   int z = conv2d_wgrad_zsplits(cs);
   at::Tensor ws;
   float* wsp = nullptr;
   if (z > 1 || out_dt != DT::F32) {
-    ws = at::empty({(int64_t)z * KH * KW * cs.Cin * cs.Cout},
+    ws = at::empty({(int64_t)z * rows * cs.Cout},
                    x.options().dtype(at::kFloat));
     wsp = ws.data_ptr<float>();
   }
-  conv2d_wgrad_launch(dt_of(x), x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
-                      out_dt, wsp, z, zero_page(x), cs, cur_stream());
-  return dw;
+  conv2d_wgrad_launch(dt_of(x), x.data_ptr(), dy.data_ptr(), out.data_ptr(),
+                      out_dt, wsp, z, zero_page(x), cs, bias, cur_stream());
+  return out;
+}
+
+at::Tensor conv2d_wgrad(const at::Tensor& x, const at::Tensor& dy, int64_t KH,
+                        int64_t KW, int64_t sh, int64_t sw, int64_t ph,
+                        int64_t pw, bool out_in_dt) {
+  return conv2d_wgrad_rows(x, dy, KH, KW, sh, sw, ph, pw, out_in_dt, false)
+      .view({KH, KW, x.size(3), dy.size(3)});
+}
+
+// weight and bias gradient from one kernel + one reduce: the bias gradient
+// sum_m dy is one more output row of the wgrad GEMM (x == 1), so dw and db
+// are views of the same tensor
+std::vector<at::Tensor> conv2d_wgrad_bias(const at::Tensor& x,
+                                          const at::Tensor& dy, int64_t KH,
+                                          int64_t KW, int64_t sh, int64_t sw,
+                                          int64_t ph, int64_t pw,
+                                          bool out_in_dt) {
+  auto out = conv2d_wgrad_rows(x, dy, KH, KW, sh, sw, ph, pw, out_in_dt, true);
+  const int64_t kout = out.size(0) - 1;
+  return {out.narrow(0, 0, kout).view({KH, KW, x.size(3), dy.size(3)}),
+          out.select(0, kout)};
 }
 
 // ---- batch norm ------------------------------------------------------------
@@ -1084,6 +1108,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd_stats", &tnn::conv2d_fwd_stats);
   m.def("conv2d_dgrad", &tnn::conv2d_dgrad);
   m.def("conv2d_wgrad", &tnn::conv2d_wgrad);
+  m.def("conv2d_wgrad_bias", &tnn::conv2d_wgrad_bias);
   m.def("bn_fwd_train", &tnn::bn_fwd_train, py::arg("x"), py::arg("gamma"),
         py::arg("beta"), py::arg("rmean"), py::arg("rvar"),
         py::arg("momentum"), py::arg("eps"), py::arg("relu"),

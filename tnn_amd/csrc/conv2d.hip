@@ -624,7 +624,8 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
 template <typename T, bool POW2>
 __launch_bounds__(THREADS, 3)  // cap VGPRs: unconstrained allocation hit 221-256 VGPR = 1-2 waves/SIMD
 __global__ void k_conv_wgrad(const T* __restrict__ X, const T* __restrict__ DY,
-                             float* __restrict__ DW, ConvShape cs) {
+                             float* __restrict__ DW, ConvShape cs,
+                             int bias_row) {
   constexpr int V = 16 / sizeof(T);
   __shared__ alignas(16) T As[BM * BK];  // rows = (kh,kw,ci), k = m
   __shared__ alignas(16) T Bs[BN * BK];  // rows = co, k = m
@@ -647,6 +648,10 @@ __global__ void k_conv_wgrad(const T* __restrict__ X, const T* __restrict__ DY,
   const int m_end = (int)((int64_t)M * (blockIdx.z + 1) / gridDim.z);
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
+  // bias gradient: tile-row 0 (one block per n-tile and split) also sums
+  // the columns of its dy tiles and writes them as slab row Kout
+  const bool colsum = bias_row && tr_ == 0;
+  float bsum = 0.0f;
   using VecT = Pack16<T>;
 
   for (int k0 = m_begin; k0 < m_end; k0 += BK) {
@@ -717,13 +722,20 @@ __global__ void k_conv_wgrad(const T* __restrict__ X, const T* __restrict__ DY,
     }
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
+    if (colsum) bsum += colsum_tile_partial(Bs);
     __syncthreads();
   }
 
-  float* out = DW + (int64_t)blockIdx.z * Kout * cs.Cout;
+  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
   epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
     if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
   });
+  if (colsum) {
+    bsum = colsum_tile_finish(bsum);
+    int col = n0 + (threadIdx.x >> 2);
+    if ((threadIdx.x & 3) == 0 && col < cs.Cout)
+      out[(int64_t)Kout * cs.Cout + col] = bsum;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -740,7 +752,8 @@ __launch_bounds__(THREADS, 3)
 __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
                                  const T* __restrict__ DY,
                                  float* __restrict__ DW,
-                                 const T* __restrict__ zero16, ConvShape cs) {
+                                 const T* __restrict__ zero16, ConvShape cs,
+                                 int bias_row) {
   constexpr int V = 16 / sizeof(T);
   constexpr int RA = BK * (BM / V) / THREADS;
   constexpr int RB = BK * (BN / V) / THREADS;
@@ -764,6 +777,8 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
   const int m_end = (int)((int64_t)M * (blockIdx.z + 1) / gridDim.z);
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
+  const bool colsum = bias_row && tr_ == 0;  // see k_conv_wgrad
+  float bsum = 0.0f;
   using VecT = Pack16<T>;
 
   // bf16: each thread owns one 8-row group x 4 consecutive m columns --
@@ -865,13 +880,163 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
     if (k0 + BK < m_end) load_tile(k0 + BK);
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
+    if (colsum) bsum += colsum_tile_partial(Bs);
     __syncthreads();
   }
 
-  float* out = DW + (int64_t)blockIdx.z * Kout * cs.Cout;
+  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
   epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
     if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
   });
+  if (colsum) {
+    bsum = colsum_tile_finish(bsum);
+    int col = n0 + (threadIdx.x >> 2);
+    if ((threadIdx.x & 3) == 0 && col < cs.Cout)
+      out[(int64_t)Kout * cs.Cout + col] = bsum;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// bf16 wgrad staged the way fwd/dgrad are: pure LDS-DMA, no staging VGPRs,
+// no LDS write instructions. Neither operand needs a transpose in memory --
+// dy is a row-major [m][Cout] tile and gathered x is [m][(kh,kw,ci)] with
+// 16-byte ci runs -- so both images are stored as they lie, m(=k)-major
+// (A [BK][BM], B [BK][BN]), and the MFMA fragments are read transposed
+// (tile_gemm.h, kmaj_off / tr_frag_issue). A lane's slot in each of its DMA
+// instructions never moves, so its (kh,kw,ci) decode is hoisted out of the
+// k-loop; per chunk only the (n,oh,ow) decode of its m-rows remains.
+// Same gate as k_conv_wgrad_vec<bf16>: all-pow2 shape, Cin%8 == Cout%8 == 0,
+// 16B-aligned tensors. Double-buffered k-loop (48 KB LDS, 3 blocks/CU): it
+// measured 3-5% ahead of the single-buffer form (24 KB) on the WRN shapes.
+// ---------------------------------------------------------------------------
+__launch_bounds__(THREADS, 2)  // <=256 regs: MFMA accumulators stay in VGPRs
+__global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
+                                const bf16* __restrict__ DY,
+                                float* __restrict__ DW,
+                                const bf16* __restrict__ zero16, ConvShape cs,
+                                int bias_row) {
+  constexpr int NA = glds_kmajor_count<BM / 8>();   // A glds per wave (4)
+  constexpr int NPER = NA + glds_kmajor_count<BN / 8>();
+  // one LDS object per buffer, named statically in the 2x-unrolled k-loop
+  __shared__ alignas(16) bf16 As0[BK * BM], As1[BK * BM];  // [m][(kh,kw,ci)]
+  __shared__ alignas(16) bf16 Bs0[BK * BN], Bs1[BK * BN];  // [m][co]
+  const int M = cs.N * cs.OH * cs.OW;
+  const int Kout = cs.KH * cs.KW * cs.Cin;
+  int tr_, tn_;
+  if ((int64_t)Kout * M > (int64_t)32 * 1024 * 1024)
+    tile::tile_remap_xcd<4>(tr_, tn_);
+  else {
+    tr_ = blockIdx.x;
+    tn_ = blockIdx.y;
+  }
+  const int r0 = tr_ * BM;
+  const int n0 = tn_ * BN;
+  const int m_begin = (int)((int64_t)M * blockIdx.z / gridDim.z);
+  const int m_end = (int)((int64_t)M * (blockIdx.z + 1) / gridDim.z);
+  const WaveCoord wc;
+  const int wm = wc.wid / WAVES_N;
+  f32x4 acc[FM][FN] = {};
+  // bias gradient (see k_conv_wgrad): the dy fragments are already in
+  // registers, so tile-row 0 sums them with one all-ones MFMA per k-step;
+  // wave (wm, wn) takes the 16 columns wcol0 + 16*wm
+  const bool colsum = bias_row && tr_ == 0;
+  f32x4 bacc = {};
+  bf16x8 ones;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
+
+  // hoisted A-side column decode, one per glds instruction of this lane
+  int a_dh[NA], a_dw[NA], a_ci[NA];  // kh-PH, kw-PW, ci (-1: past Kout)
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int row = 4 * (wc.wid * NA + i) + wc.lane / 16;
+    const int gr = r0 + 8 * ((wc.lane % 16) ^ kmaj_key<16>(row));
+    int kh, kw;
+    kdecode(gr >> cs.d_cin.lg, cs, kh, kw);
+    a_dh[i] = kh - cs.PH;
+    a_dw[i] = kw - cs.PW;
+    a_ci[i] = gr < Kout ? (gr & (cs.Cin - 1)) : -1;
+  }
+
+  auto stage = [&](int k0, bf16* a_img, bf16* b_img) {
+    glds_stage_kmajor<BM / 8>(a_img, wc,
+                              [&](int i, int row, int) -> const bf16* {
+      // branch-free: an invalid lane's address is computed but never used
+      const int gm = k0 + row;
+      const int n = gm >> cs.d_ohow.lg;
+      const int rem = gm & (cs.OH * cs.OW - 1);
+      const int oh = rem >> cs.d_ow.lg, ow = rem & (cs.OW - 1);
+      const int ih = oh * cs.SH + a_dh[i];
+      const int iw = ow * cs.SW + a_dw[i];
+      const bool ok = gm < m_end && a_ci[i] >= 0 &&
+                      (unsigned)ih < (unsigned)cs.H &&
+                      (unsigned)iw < (unsigned)cs.W;
+      // all-pow2 gate: the pixel index and the *Cin are shifts
+      const int pix = (n << cs.d_hw.lg) + (ih << cs.d_w.lg) + iw;
+      const bf16* p = X + (((int64_t)pix << cs.d_cin.lg) + a_ci[i]);
+      return ok ? p : zero16;
+    });
+    glds_stage_kmajor<BN / 8>(b_img, wc,
+                              [&](int, int row, int ch) -> const bf16* {
+      const int gm = k0 + row, gn = n0 + 8 * ch;
+      const bf16* p = DY + (((int64_t)gm << cs.d_cout.lg) + gn);
+      return gm < m_end && gn < cs.Cout ? p : zero16;
+    });
+  };
+  auto compute = [&](const bf16* a_img, const bf16* b_img) {
+#pragma unroll
+    for (int ks = 0; ks < BK / 32; ++ks) {
+      TrFrag a[FM], b[FN];
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+        a[fm] = tr_frag_issue<BM / 8>(a_img, ks * 32, wc.wrow0 + fm * 16,
+                                      wc.lane);
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+        b[fn] = tr_frag_issue<BN / 8>(b_img, ks * 32, wc.wcol0 + fn * 16,
+                                      wc.lane);
+      tr_frags_wait(a, b);
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn)
+          acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[fm].get(), b[fn].get(), acc[fm][fn], 0, 0, 0);
+      if (colsum)
+        bacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            ones, wm ? b[1].get() : b[0].get(), bacc, 0, 0, 0);
+    }
+  };
+
+  // chunk k0 sits in (a_cur, b_cur); the next one streams into the other
+  // buffer under this chunk's MFMAs
+  auto step = [&](int k0, bf16* a_cur, bf16* b_cur, bf16* a_nxt,
+                  bf16* b_nxt) {
+    if (k0 + BK < m_end) {
+      stage(k0 + BK, a_nxt, b_nxt);
+      wait_vmcnt<NPER>();   // this chunk landed; the next stays in flight
+    } else {
+      wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    compute(a_cur, b_cur);
+    __builtin_amdgcn_s_barrier();   // cur free for the chunk after next
+  };
+  if (m_begin < m_end) stage(m_begin, As0, Bs0);
+  for (int k0 = m_begin; k0 < m_end; k0 += 2 * BK) {
+    step(k0, As0, Bs0, As1, Bs1);
+    if (k0 + BK < m_end) step(k0 + BK, As1, Bs1, As0, Bs0);
+  }
+
+  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
+  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
+    if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
+  });
+  if (colsum && wc.lane < 16) {
+    // every row of bacc is the column sum; lanes 0-15 hold row 0
+    int col = n0 + wc.wcol0 + 16 * wm + wc.lane;
+    if (col < cs.Cout) out[(int64_t)Kout * cs.Cout + col] = bacc[0];
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1158,8 +1323,11 @@ int conv2d_wgrad_zsplits(const ConvShape& cs) {
 
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
-                         const ConvShape& cs, hipStream_t s) {
+                         const ConvShape& cs, bool bias, hipStream_t s) {
   int Kout = cs.KH * cs.KW * cs.Cin;
+  // bias: dw_out and every slab carry one more row, [Kout+1][Cout], whose
+  // last row is the bias gradient sum_m dy (summed by the tile-row-0 blocks)
+  const int bias_row = bias ? 1 : 0;
   // bf16 output always goes through the (casting) reduce; fp32 with z==1
   // writes the slab target directly
   bool direct = z == 1 && out_dt == DT::F32;
@@ -1172,27 +1340,43 @@ void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
     if (vec) {
       hipLaunchKernelGGL((k_conv_wgrad_vec<float, true>), grid, dim3(THREADS),
                          0, s, (const float*)x, (const float*)dy, target,
-                         (const float*)zero16, cs);
+                         (const float*)zero16, cs, bias_row);
     } else {
       auto kern = p2 ? k_conv_wgrad<float, true> : k_conv_wgrad<float, false>;
       hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const float*)x,
-                         (const float*)dy, target, cs);
+                         (const float*)dy, target, cs, bias_row);
     }
   } else {
     bool vec = p2 && cs.Cin % 8 == 0 && cs.Cout % 8 == 0 &&
                (((uintptr_t)x & 15) == 0) && (((uintptr_t)dy & 15) == 0);
-    if (vec) {
+    // TNN_WGRAD_TR=0 (read once) routes bf16 back to the register-staged
+    // kernel, so both paths can be compared from one build
+    static const bool tr_on = []() {
+      const char* e = getenv("TNN_WGRAD_TR");
+      return !(e && atoi(e) == 0);
+    }();
+    if (vec && tr_on) {
+      hipLaunchKernelGGL(k_conv_wgrad_tr, grid, dim3(THREADS), 0, s,
+                         (const bf16*)x,
+                         (const bf16*)dy, target, (const bf16*)zero16, cs,
+                         bias_row);
+    } else if (vec) {
       hipLaunchKernelGGL((k_conv_wgrad_vec<bf16, true>), grid, dim3(THREADS),
                          0, s, (const bf16*)x, (const bf16*)dy, target,
-                         (const bf16*)zero16, cs);
+                         (const bf16*)zero16, cs, bias_row);
     } else {
       auto kern = p2 ? k_conv_wgrad<bf16, true> : k_conv_wgrad<bf16, false>;
       hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const bf16*)x,
-                         (const bf16*)dy, target, cs);
+                         (const bf16*)dy, target, cs, bias_row);
     }
   }
+  // the reduce kernel (and so dw's summation order) is chosen from dw's own
+  // size: with Cout % 4 == 0 the extra row never changes dw's bits (else the
+  // longer output can fall off the float4 reduce; still deterministic)
   if (!direct)
-    splitk_reduce_launch(ws, dw_out, out_dt, z, (int64_t)Kout * cs.Cout, s);
+    splitk_reduce_launch(ws, dw_out, out_dt, z,
+                         (int64_t)(Kout + bias_row) * cs.Cout, s,
+                         (int64_t)Kout * cs.Cout);
 }
 
 void transpose_w_launch(DT dt, const void* w, void* w_t, int KH, int KW,

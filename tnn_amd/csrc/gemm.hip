@@ -906,27 +906,32 @@ __global__ void k_splitk_fold(const float4* __restrict__ ws,
 
 template <typename OUT>
 static void splitk_fold_launch(const float4* ws, OUT* out, int z, int64_t n4,
-                               hipStream_t s) {
+                               hipStream_t s, int64_t n4_shape) {
 #define FOLD_CASE(CPB)                                                    \
   hipLaunchKernelGGL((k_splitk_fold<OUT, CPB>),                           \
                      dim3((unsigned)((n4 + CPB - 1) / CPB)), dim3(256), 0, \
                      s, ws, out, z, n4)
-  if (n4 >= 128 * 32) FOLD_CASE(32);
-  else if (n4 >= 128 * 16) FOLD_CASE(16);
-  else if (n4 >= 128 * 8) FOLD_CASE(8);
-  else if (n4 >= 128 * 4) FOLD_CASE(4);
-  else if (n4 >= 128 * 2) FOLD_CASE(2);
+  if (n4_shape >= 128 * 32) FOLD_CASE(32);
+  else if (n4_shape >= 128 * 16) FOLD_CASE(16);
+  else if (n4_shape >= 128 * 8) FOLD_CASE(8);
+  else if (n4_shape >= 128 * 4) FOLD_CASE(4);
+  else if (n4_shape >= 128 * 2) FOLD_CASE(2);
   else FOLD_CASE(1);
 #undef FOLD_CASE
 }
 
+// n_shape (default n): the element count the kernel and its fold width are
+// chosen for. A caller that appends rows to an output passes the original
+// size, so the original elements keep their summation order bit for bit.
 void splitk_reduce_launch(const float* ws, void* out, DT out_dt, int z,
-                          int64_t n, hipStream_t s) {
+                          int64_t n, hipStream_t s, int64_t n_shape) {
+  if (n_shape <= 0) n_shape = n;
   dispatch_dt(out_dt, [&](auto tag) {
     using OUT = typename decltype(tag)::type;
-    if ((n & 3) == 0 && n < 4 * 32768 && z >= 8) {
+    if ((n & 3) == 0 && (n_shape & 3) == 0 && n_shape < 4 * 32768 && z >= 8) {
       // small output x deep z: parallelize over z (see k_splitk_fold)
-      splitk_fold_launch((const float4*)ws, (OUT*)out, z, n >> 2, s);
+      splitk_fold_launch((const float4*)ws, (OUT*)out, z, n >> 2, s,
+                         n_shape >> 2);
     } else if ((n & 3) == 0) {
       int64_t n4 = n >> 2;
       int blocks = (int)std::min<int64_t>((n4 + 255) / 256, (int64_t)2048);

@@ -71,7 +71,7 @@ void gemm_tn_launch(DT dt, const void* a, const void* b, void* c_out,
                     DT out_dt, float* ws, int z, const void* zero16, int M,
                     int N, int K, hipStream_t s);
 void splitk_reduce_launch(const float* ws, void* out, DT out_dt, int z,
-                          int64_t n, hipStream_t s);
+                          int64_t n, hipStream_t s, int64_t n_shape = 0);
 void mfma_selftest_launch(const void* a_bf16, const void* b_bf16, float* d,
                           hipStream_t s);
 void mfma_selftest_f32_launch(const float* a, const float* b, float* d,
@@ -132,7 +132,7 @@ void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
 int conv2d_wgrad_zsplits(const ConvShape& cs);
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
-                         const ConvShape& cs, hipStream_t s);
+                         const ConvShape& cs, bool bias, hipStream_t s);
 void transpose_w_launch(DT dt, const void* w, void* w_t, int KH, int KW,
                         int Cin, int Cout, hipStream_t s);
 

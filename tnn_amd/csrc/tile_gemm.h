@@ -215,6 +215,143 @@ DEV void mfma_compute_tile(const float* As, const float* Bs, const WaveCoord& w,
   }
 }
 
+// ---- k-major bf16 images + transposed fragment reads (gfx950) -------------
+// A TN product (wgrad: both operands lie k-major in memory, [k][row]) needs
+// no transpose on the way INTO LDS: the image keeps the memory layout,
+// [BK k-rows][NCH 16-byte chunks], filled by 16B LDS-DMA, and
+// ds_read_b64_tr_b16 transposes on the way out -- per 16-lane group it
+// fetches a 4 k-row x 16-column block and hands lane i column i, i.e. 4
+// k-values of one operand row; two reads make a 16x16x32 fragment's 8.
+//
+// Bank rule (bank = (addr/4) % 64, conflicts counted per 32-lane half): a
+// half's two groups read blocks 8 k-rows apart in the same 16 columns, so
+// its 32 lanes (q = k-row in block, b = group, p = 8-byte piece of the 32-byte
+// column run) must cover 32 distinct 8-byte slots of a 256-byte bank line.
+//   NCH=16 (256-B rows, one bank line per row): slot = 2*(ch^key) + (p&1);
+//     key = ((row&3)<<2) | ((row>>2)&3) puts q in chunk bits 2-3 and b (row
+//     bit 3) in bit 1, the fragment's p>>1 is bit 0: 16 distinct chunks.
+//   NCH=8 (128-B rows, two rows per bank line): slot = 16*(row&1) +
+//     2*(ch^key) + (p&1); key = (row&2) | (((row>>3)&1)<<2) puts q>>1 in
+//     chunk bit 1 and b in bit 2: 8 distinct chunks in each line half.
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+
+template <int NCH>
+DEV int kmaj_key(int row) {
+  static_assert(NCH == 16 || NCH == 8, "128- or 64-column bf16 image");
+  if constexpr (NCH == 16) return ((row & 3) << 2) | ((row >> 2) & 3);
+  else return (row & 2) | (((row >> 3) & 1) << 2);
+}
+
+// byte offset of 16-byte chunk ch of k-row `row`; the store (DMA source
+// swizzle) and every read go through this one function
+template <int NCH>
+DEV int kmaj_off(int row, int ch) {
+  return 16 * NCH * row + 16 * (ch ^ kmaj_key<NCH>(row));
+}
+
+// fills a [BK][NCH*8] image: each glds instruction covers a lane-linear
+// 1 KiB region, lane -> (k-row, physical chunk), and asks
+// addr(i, row, ch) for the LOGICAL chunk that belongs there (16B-aligned
+// source or the zero page; no exec masking). i = the wave's instruction
+// index, so callers can hoist per-instruction state out of the k-loop: a
+// lane's (row-in-tile, ch) never changes from chunk to chunk.
+template <int NCH, typename AddrFn>
+DEV void glds_stage_kmajor(bf16* img, const WaveCoord& w, AddrFn&& addr) {
+  constexpr int RPK = 64 / NCH;                 // k-rows per 1 KiB region
+  constexpr int NPW = BK * NCH * 16 / 1024 / 4;  // regions per wave
+#pragma unroll
+  for (int i = 0; i < NPW; ++i) {
+    // the DMA's LDS base is a scalar operand: tell the compiler the wave
+    // id is uniform, or it wraps every glds in a waterfall loop
+    const int j = __builtin_amdgcn_readfirstlane(w.wid) * NPW + i;
+    const int row = RPK * j + w.lane / NCH;
+    const int ch = (w.lane % NCH) ^ kmaj_key<NCH>(row);
+    const bf16* src = addr(i, row, ch);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)&img[j * 512], 16, 0,
+        0);
+  }
+}
+template <int NCH>
+constexpr int glds_kmajor_count() { return BK * NCH * 16 / 1024 / 4; }
+
+// 16x16x32 MFMA operand fragment for image columns col0..col0+15 over
+// k-rows krow0..krow0+31. Lane group g holds k-rows krow0 + 16*(g>>1) +
+// 8*(g&1) + {0..7}: any k order is valid as long as A and B share it.
+// EXEC must be all ones here (the gather crosses lanes).
+//
+// The reads are inline asm, not the ds_read_tr16 builtin: before an LDS
+// read it knows of, the compiler drains every in-flight LDS-DMA it cannot
+// prove disjoint (s_waitcnt vmcnt(0) -- seen right after the barrier with
+// the builtin, even with one LDS object per buffer), which serialises a
+// double-buffered k-loop. What it cannot see it does not wait for, so the
+// caller owns the wait too: issue all fragments, then tr_frags_wait().
+struct TrFrag {
+  s16x4 lo, hi;
+  DEV bf16x8 get() const {
+    s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(bf16x8, v);
+  }
+};
+
+template <int NCH>
+DEV TrFrag tr_frag_issue(const bf16* img, int krow0, int col0, int lane) {
+  typedef __attribute__((address_space(3))) const char* lds_p;
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int row = krow0 + 16 * (g >> 1) + 8 * (g & 1) + q;
+  const int ch = (col0 >> 3) + (p >> 1);
+  const unsigned base = (unsigned)(size_t)(lds_p)(const char*)img + 8 * (p & 1);
+  TrFrag f;
+  asm volatile("ds_read_b64_tr_b16 %0, %1"
+               : "=v"(f.lo) : "v"(base + kmaj_off<NCH>(row, ch)) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1"
+               : "=v"(f.hi) : "v"(base + kmaj_off<NCH>(row + 4, ch)) : "memory");
+  return f;
+}
+
+// lgkmcnt(0) for the fragments of one k-step; the "+v" operands tie every
+// fragment to the wait, so no MFMA that consumes one is scheduled above it
+DEV void tr_frags_wait(TrFrag (&a)[FM], TrFrag (&b)[FN]) {
+  static_assert(FM == 4 && FN == 2, "operand list below");
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+v"(a[0].lo), "+v"(a[0].hi), "+v"(a[1].lo), "+v"(a[1].hi),
+                 "+v"(a[2].lo), "+v"(a[2].hi), "+v"(a[3].lo), "+v"(a[3].hi),
+                 "+v"(b[0].lo), "+v"(b[0].hi), "+v"(b[1].lo), "+v"(b[1].hi)
+               :: "memory");
+}
+
+// ---- column sums of a transposed B tile Bs[BN][BK] ------------------------
+// A conv bias gradient (db[co] = sum_m dy[m][co]) is wgrad with x == 1, and
+// the dy tile already sits in LDS as Bs[co][m]. Four threads share a column
+// and sum a quarter of its BK values each in fp32 (fixed order, so the sum
+// is deterministic); the caller keeps ONE running float per thread. (An
+// all-ones MFMA does the same sum but needs an f32x4 accumulator plus two
+// fragments: 122 -> 132 VGPR in k_conv_wgrad_vec<bf16>, 4 -> 3 waves/SIMD.)
+static_assert(THREADS == 4 * BN, "4 threads per B-tile column");
+template <typename T>
+DEV float colsum_tile_partial(const T* Bs) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const int co = threadIdx.x >> 2;
+  const int m0 = (threadIdx.x & 3) * (BK / 4);
+  float s = 0.0f;
+#pragma unroll
+  for (int c = 0; c < BK / 4; c += V) {
+    Pack16<T> v = *(const Pack16<T>*)&Bs[lds_off<T>(co, m0 + c)];
+#pragma unroll
+    for (int j = 0; j < V; ++j) s += VecIO<T>::to_f32(v.e[j]);
+  }
+  return s;
+}
+
+// folds the four per-thread partials of a column; valid where
+// (threadIdx.x & 3) == 0, for tile column threadIdx.x >> 2
+DEV float colsum_tile_finish(float s) {
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  return s;
+}
+
 // ---- epilogue: C/D fragment map col=lane&15, row=(lane>>4)*4+j ------------
 // Visits every accumulator element with its global (row, col).
 template <typename F>

@@ -111,14 +111,22 @@ class _Conv2dNHWC(torch.autograd.Function):
                                   ctx.stride[0], ctx.stride[1], ctx.padding[0], ctx.padding[1])
             if x.shape[-1] != ctx.cin:
                 dx = dx[..., :ctx.cin].contiguous()
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            dw = ext.conv2d_wgrad(x, dy, w.shape[0], w.shape[1],
-                                  ctx.stride[0], ctx.stride[1], ctx.padding[0],
-                                  ctx.padding[1], w.dtype == x.dtype)
+            args = (x, dy, w.shape[0], w.shape[1], ctx.stride[0],
+                    ctx.stride[1], ctx.padding[0], ctx.padding[1],
+                    w.dtype == x.dtype)
+            if want_db:
+                # the bias gradient rides along as one more wgrad output
+                # row: no second pass over dy, no separate cast
+                dw, db = ext.conv2d_wgrad_bias(*args)
+                db = db.to(dy.dtype)  # no-op when the reduce already cast
+            else:
+                dw = ext.conv2d_wgrad(*args)
             if x.shape[-1] != ctx.cin:
                 dw = dw[:, :, :ctx.cin].contiguous()
             dw = dw.to(w.dtype)  # no-op when the reduce already cast
-        if ctx.has_bias and ctx.needs_input_grad[2]:
+        elif want_db:
             db = ext.colsum(dy.reshape(-1, dy.shape[-1]))
         return dx, dw, db, None, None, None, None
 
