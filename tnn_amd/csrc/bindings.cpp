@@ -370,9 +370,10 @@ at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
 }
 
 // conv fwd + fused per-channel sum/sumsq for a following train-mode BN
-// (linear act). Returns {y, stats[2, Cout]}; stats is EMPTY when the
-// double-buffered kernel (the only one carrying the stats epilogue) is not
-// eligible -- callers fall back to the separate BN stats pass.
+// (linear act). Returns {y, stats[2, Cout]}; stats is EMPTY when no
+// DMA-staged kernel (k_conv_fwd_db / k_conv_fwd_sb, the ones carrying the
+// stats epilogue) is eligible -- callers fall back to the separate BN stats
+// pass.
 std::vector<at::Tensor> conv2d_fwd_stats(const at::Tensor& x,
                                          const at::Tensor& w,
                                          const c10::optional<at::Tensor>& bias,
@@ -385,8 +386,9 @@ std::vector<at::Tensor> conv2d_fwd_stats(const at::Tensor& x,
   auto y = at::empty({cs.N, cs.OH, cs.OW, cs.Cout}, x.options());
   const void* bp = bias.has_value() ? bias->data_ptr() : nullptr;
   if (!conv2d_fwd_wants_db(dt_of(x), x.data_ptr(), cs)) {
-    // stats fusion needs the db kernel; ineligible shapes (e.g. K > 2304)
-    // still must COMPUTE y via the plain path. (Round-1 latent bug: this
+    // stats fusion needs a DMA-staged kernel; ineligible shapes (non-pow2
+    // dims, unaligned x, fp32 with K > 2304, TNN_FWD_DB=0) still must
+    // COMPUTE y via the plain path. (Round-1 latent bug: this
     // early return handed back uninitialized y — garbage activations for
     // every 512-channel conv under BN training.)
     conv2d_fwd_launch(dt_of(x), x.data_ptr(), w.data_ptr(), nullptr, bp,

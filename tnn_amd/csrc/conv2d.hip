@@ -52,22 +52,165 @@ DEV void kdecode(int kidx, const ConvShape& cs, int& kh, int& kw) {
 }
 
 // ---------------------------------------------------------------------------
+// double-buffered k-loop shared by k_conv_fwd_db and k_conv_dgrad_db, fp32
+// and bf16 (all-pow2 shapes, gathered channel count C = 1 << lgC a multiple
+// of the 16-byte vector width).
+//
+// A is gathered from an NHWC tensor with 1 << lgSW columns per image row: tile
+// row gm reads pixel (n, p + dh, q + dw), where (n, p, q) depend on the row
+// only and the tap (dh, dw, channel c) on the k index only. B is a row-major
+// [brows][bstride] matrix read at column bcol(k).
+//   row(gm, noff, p, q) -> row < M; noff = element offset of image n
+//   tap(gk, dh, dw, c, bcol)   decodes one k index (scalar or per lane)
+//   at(p, q, dh, dw, sh, sw) -> pixel valid; (sh, sw) = source pixel
+// Staging: a lane's slot in each of its DMA instructions never moves, so the
+// row decode, row validity and base pointers are computed once, before the
+// loop. With C % BK == 0 a chunk lies in one (kh,kw) slice: its tap is
+// decoded once, in scalar registers. Narrower C (and with it the ragged last
+// chunk) decodes per instruction. Invalid lanes select the zero page
+// branch-free: the address is computed and dropped.
+// K: no DMA ever reads at or past k index K. K == 0 is a real case (a
+// stride-2 parity class of a 1x1 kernel has no tap): nothing is staged and
+// acc stays zero. On the one-tap-per-chunk path K is a multiple of BK, so the
+// chunk-level test kk0 < K covers every lane; the per-instruction path tests
+// each lane's own k index.
+// Sync: counted vmcnt + raw s_barrier only. The bf16 fragment reads are
+// asm-issued (tile_gemm.h, rm_frag_issue), so the next chunk's DMAs stay in
+// flight under this chunk's MFMAs; the fp32 reads stay visible to the
+// compiler, which drains the DMAs before them as it always did. Chunk, k-step
+// and MFMA order are those of the single-buffer kernels: the accumulators are
+// bitwise the same.
+template <bool DB, typename T, typename RowFn, typename TapFn, typename AtFn>
+DEV void conv_db_kloop(T* As0, T* As1, T* Bs0, T* Bs1,
+                       const WaveCoord& wc, f32x4 acc[FM][FN],
+                       const T* __restrict__ asrc, int lgSW, int lgC,
+                       const T* __restrict__ bsrc, int64_t bstride,
+                       int brows, int m0, int n0, int K,
+                       const T* __restrict__ zero16, RowFn&& row,
+                       TapFn&& tap, AtFn&& at) {
+  constexpr int NA = glds_count<T, BM>();   // A glds per wave
+  constexpr int NB = glds_count<T, BN>();   // B glds per wave
+  constexpr int NPER = NA + NB;
+  const int wid = __builtin_amdgcn_readfirstlane(wc.wid);
+  const bool uni = lgC >= 6;   // C % BK == 0: one tap per chunk
+
+  const T* ab[NA];
+  int ap[NA], aq[NA];          // ap very negative: row past M, never valid
+  const T* bb[NB];
+  bool bok[NB];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int j = wid * NA + i;
+    int64_t noff;
+    int p, q;
+    const bool ok = row(m0 + glds_row<T>(j, wc.lane), noff, p, q);
+    ab[i] = asrc + noff + (uni ? glds_kk<T>(j, wc.lane) : 0);
+    ap[i] = ok ? p : -(1 << 28);
+    aq[i] = q;
+  }
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int j = wid * NB + i;
+    const int gn = n0 + glds_row<T>(j, wc.lane);
+    bok[i] = gn < brows;
+    bb[i] = bsrc + (int64_t)gn * bstride + (uni ? glds_kk<T>(j, wc.lane) : 0);
+  }
+
+  auto a_ptr = [&](int i, int dh, int dw, int c, bool& ok) {
+    int sh, sw;
+    ok = at(ap[i], aq[i], dh, dw, sh, sw);
+    const unsigned pix = ((unsigned)sh << lgSW) + (unsigned)sw;
+    return ab[i] + (int)((pix << lgC) + (unsigned)c);
+  };
+  auto stage = [&](int t, T* a_img, T* b_img) {
+    const int kk0 = t * BK;
+    if (uni) {
+      int dh, dw, c, bcol;
+      tap(kk0, dh, dw, c, bcol);
+      const bool kin = kk0 < K;   // wave-uniform
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        bool ok;
+        const T* p = a_ptr(i, dh, dw, c, ok);
+        glds_issue(a_img, wid * NA + i, (ok & kin) ? p : zero16);
+      }
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+        glds_issue(b_img, wid * NB + i,
+                   (bok[i] & kin) ? bb[i] + bcol : zero16);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int gk = kk0 + glds_kk<T>(wid * NA + i, wc.lane);
+        int dh, dw, c, bcol;
+        tap(gk, dh, dw, c, bcol);
+        bool ok;
+        const T* p = a_ptr(i, dh, dw, c, ok);
+        glds_issue(a_img, wid * NA + i, (ok & (gk < K)) ? p : zero16);
+      }
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const int gk = kk0 + glds_kk<T>(wid * NB + i, wc.lane);
+        int dh, dw, c, bcol;
+        tap(gk, dh, dw, c, bcol);
+        glds_issue(b_img, wid * NB + i,
+                   (bok[i] & (gk < K)) ? bb[i] + bcol : zero16);
+      }
+    }
+  };
+  // chunk t sits in (a_cur, b_cur); the next one streams into the other
+  // buffer under this chunk's MFMAs
+  const int nch = (K + BK - 1) / BK;
+  if (nch == 0) return;
+  auto compute = [&](const T* a_img, const T* b_img) {
+    if constexpr (sizeof(T) == 2)
+      mfma_compute_tile_nofence(a_img, b_img, wc, acc);
+    else
+      mfma_compute_tile(a_img, b_img, wc, acc);
+  };
+  auto step = [&](int t, T* a_cur, T* b_cur, T* a_nxt, T* b_nxt) {
+    if (t + 1 < nch) {
+      stage(t + 1, a_nxt, b_nxt);
+      wait_vmcnt<NPER>();   // chunk t landed; t+1 stays in flight
+    } else {
+      wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    compute(a_cur, b_cur);
+    __builtin_amdgcn_s_barrier();   // cur free for the t+2 stage
+  };
+  if constexpr (DB) {
+    stage(0, As0, Bs0);
+    for (int t = 0; t < nch; t += 2) {
+      step(t, As0, Bs0, As1, Bs1);
+      if (t + 1 < nch) step(t + 1, As1, Bs1, As0, Bs0);
+    }
+  } else {
+    // single buffer (As1 / Bs1 unused): half the LDS, twice the resident
+    // blocks, no overlap inside a block
+    for (int t = 0; t < nch; ++t) {
+      stage(t, As0, Bs0);
+      wait_vmcnt<0>();
+      __builtin_amdgcn_s_barrier();
+      compute(As0, Bs0);
+      __builtin_amdgcn_s_barrier();
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // double-buffered pure-glds forward: both operands DMA straight to LDS
 // (weights pre-transposed to [Cout, K] so B rows are k-contiguous), the
 // next chunk's DMAs overlap the current chunk's MFMAs. Counted
 // s_waitcnt vmcnt + raw s_barrier per the CDNA4 glds idiom -- a
 // __syncthreads() here would drain the in-flight next-chunk DMAs.
-template <typename T, bool POW2, bool STATS = false>
-__launch_bounds__(THREADS)
-__global__ void k_conv_fwd_db(const T* __restrict__ X,
-                              const T* __restrict__ WT2,
-                              const float* __restrict__ bias_f32,
-                              const T* __restrict__ bias_t, T* __restrict__ Y,
-                              const T* __restrict__ zero16, ConvShape cs,
-                              int act_kind, float* __restrict__ stats) {
-  __shared__ alignas(16) T As[2][BM * BK];
-  __shared__ alignas(16) T Bs[2][BN * BK];
-
+template <typename T, bool POW2, bool STATS, bool DB>
+DEV void conv_fwd_glds_tile(const T* __restrict__ X,
+                            const T* __restrict__ WT2,
+                            const float* __restrict__ bias_f32,
+                            const T* __restrict__ bias_t, T* __restrict__ Y,
+                            const T* __restrict__ zero16, const ConvShape& cs,
+                            int act_kind, float* __restrict__ stats) {
   const int M = cs.N * cs.OH * cs.OW;
   const int K = cs.KH * cs.KW * cs.Cin;
   int tm_, tn_;
@@ -85,48 +228,36 @@ __global__ void k_conv_fwd_db(const T* __restrict__ X,
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
 
-  auto a_src = [&](int kk0, int rl, int kk) -> const T* {
-    int gm = m0 + rl, gk = kk0 + kk;
-    if (gm >= M || gk >= K) return zero16;
-    int n = idiv<POW2>(gm, cs.d_ohow);
-    int rem = gm - n * (cs.OH * cs.OW);
-    int oh = idiv<POW2>(rem, cs.d_ow), ow = rem - oh * cs.OW;
-    int ci = imod<POW2>(gk, cs.d_cin);
-    int kidx = idiv<POW2>(gk, cs.d_cin);
-    int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-    int ih = oh * cs.SH - cs.PH + kh;
-    int iw = ow * cs.SW - cs.PW + kw;
-    if (ih < 0 || ih >= cs.H || iw < 0 || iw >= cs.W) return zero16;
-    return &X[(((int64_t)n * cs.H + ih) * cs.W + iw) * cs.Cin + ci];
+  auto row = [&](int gm, int64_t& noff, int& p, int& q) {
+    const int n = gm >> cs.d_ohow.lg;
+    const int rem = gm & (cs.OH * cs.OW - 1);
+    p = (rem >> cs.d_ow.lg) * cs.SH - cs.PH;
+    q = (rem & (cs.OW - 1)) * cs.SW - cs.PW;
+    noff = (int64_t)n << (cs.d_hw.lg + cs.d_cin.lg);
+    return gm < M;
   };
-  auto b_src = [&](int kk0, int rl, int kk) -> const T* {
-    int gn = n0 + rl, gk = kk0 + kk;
-    if (gn >= cs.Cout || gk >= K) return zero16;
-    return &WT2[(int64_t)gn * K + gk];
+  auto tap = [&](int gk, int& dh, int& dw, int& c, int& bcol) {
+    kdecode(gk >> cs.d_cin.lg, cs, dh, dw);
+    c = gk & (cs.Cin - 1);
+    bcol = gk;
   };
-  auto stage = [&](int t, int which) {
-    int kk0 = t * BK;
-    glds_stage<T, BM>(As[which], wc,
-                      [&](int rl, int kk) { return a_src(kk0, rl, kk); });
-    glds_stage<T, BN>(Bs[which], wc,
-                      [&](int rl, int kk) { return b_src(kk0, rl, kk); });
+  auto at = [&](int p, int q, int dh, int dw, int& ih, int& iw) {
+    ih = p + dh;
+    iw = q + dw;
+    return (unsigned)ih < (unsigned)cs.H && (unsigned)iw < (unsigned)cs.W;
   };
-  constexpr int NPER = glds_count<T, BM>() + glds_count<T, BN>();
-
-  const int nch = (K + BK - 1) / BK;
-  stage(0, 0);
-  for (int t = 0; t < nch; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < nch) {
-      stage(t + 1, cur ^ 1);
-      wait_vmcnt<NPER>();   // chunk t landed; t+1 stays in flight
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    mfma_compute_tile(As[cur], Bs[cur], wc, acc);
-    __builtin_amdgcn_s_barrier();   // cur free for the t+2 stage
+  if constexpr (DB) {
+    // one LDS object per buffer, named statically in the 2x-unrolled loop
+    __shared__ alignas(16) T As0[BM * BK], As1[BM * BK];
+    __shared__ alignas(16) T Bs0[BN * BK], Bs1[BN * BK];
+    conv_db_kloop<true>(As0, As1, Bs0, Bs1, wc, acc, X, cs.d_w.lg,
+                        cs.d_cin.lg, WT2, (int64_t)K, cs.Cout, m0, n0, K,
+                        zero16, row, tap, at);
+  } else {
+    __shared__ alignas(16) T As0[BM * BK], Bs0[BN * BK];
+    conv_db_kloop<false>(As0, As0, Bs0, Bs0, wc, acc, X, cs.d_w.lg,
+                         cs.d_cin.lg, WT2, (int64_t)K, cs.Cout, m0, n0, K,
+                         zero16, row, tap, at);
   }
 
   epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
@@ -177,6 +308,33 @@ __global__ void k_conv_fwd_db(const T* __restrict__ X,
       }
     }
   }
+}
+
+template <typename T, bool POW2, bool STATS = false>
+__launch_bounds__(THREADS)
+__global__ void k_conv_fwd_db(const T* __restrict__ X,
+                              const T* __restrict__ WT2,
+                              const float* __restrict__ bias_f32,
+                              const T* __restrict__ bias_t, T* __restrict__ Y,
+                              const T* __restrict__ zero16, ConvShape cs,
+                              int act_kind, float* __restrict__ stats) {
+  conv_fwd_glds_tile<T, POW2, STATS, true>(X, WT2, bias_f32, bias_t, Y, zero16,
+                                           cs, act_kind, stats);
+}
+
+// the same tile on one LDS buffer pair for the long k-loops past the double
+// buffer's gate: 24 KB LDS, 72 VGPR + 32 AGPR, register-limited at 4 blocks
+// per CU (the double buffer: 3)
+template <bool STATS>
+__launch_bounds__(THREADS)
+__global__ void k_conv_fwd_sb(const bf16* __restrict__ X,
+                              const bf16* __restrict__ WT2,
+                              const bf16* __restrict__ bias_t,
+                              bf16* __restrict__ Y,
+                              const bf16* __restrict__ zero16, ConvShape cs,
+                              int act_kind, float* __restrict__ stats) {
+  conv_fwd_glds_tile<bf16, true, STATS, false>(X, WT2, nullptr, bias_t, Y,
+                                               zero16, cs, act_kind, stats);
 }
 
 // ---------------------------------------------------------------------------
@@ -501,9 +659,6 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
                                 const T* __restrict__ WT2D,
                                 T* __restrict__ DX,
                                 const T* __restrict__ zero16, ConvShape cs) {
-  __shared__ alignas(16) T As[2][BM * BK];
-  __shared__ alignas(16) T Bs[2][BN * BK];
-
   const int cls_a = S2 ? ((int)blockIdx.z >> 1) : 0;
   const int cls_b = S2 ? ((int)blockIdx.z & 1) : 0;
   const int start_h = S2 ? ((cls_a + cs.PH) & 1) : 0;
@@ -530,77 +685,58 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
 
-  auto a_src = [&](int kk0, int rl, int kk) -> const T* {
-    int gm = m0 + rl, gk = kk0 + kk;
-    if (gm >= M || gk >= K) return zero16;
-    int n = idiv<POW2>(gm, cs.d_hw);
-    int rem = gm - n * (Hc * Wc);
-    int ih = idiv<POW2>(rem, cs.d_w), iw = rem - ih * Wc;
-    int co = imod<POW2>(gk, cs.d_cout);
-    int kidx = idiv<POW2>(gk, cs.d_cout);
-    if constexpr (S2) {
-      ih = 2 * ih + cls_a;
-      iw = 2 * iw + cls_b;
-      int kwi = kidx & (nkw - 1);
-      int khi = nkw == 2 ? (kidx >> 1) : kidx;
-      int kh = start_h + 2 * khi, kw = start_w + 2 * kwi;
-      int th = ih + cs.PH - kh, tw = iw + cs.PW - kw;
-      if (th < 0 || tw < 0) return zero16;
-      int oh = th >> 1, ow = tw >> 1;
-      if (oh >= cs.OH || ow >= cs.OW) return zero16;
-      return &DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) * cs.Cout + co];
-    } else {
-      int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-      int th = ih + cs.PH - kh, tw = iw + cs.PW - kw;
-      if constexpr (S1) {  // stride 1: no divisibility test, oh == th
-        if (th < 0 || tw < 0 || th >= cs.OH || tw >= cs.OW) return zero16;
-        return &DY[(((int64_t)n * cs.OH + th) * cs.OW + tw) * cs.Cout + co];
-      } else {
-        if (th < 0 || tw < 0 || th % cs.SH || tw % cs.SW) return zero16;
-        int oh = th / cs.SH, ow = tw / cs.SW;
-        if (oh >= cs.OH || ow >= cs.OW) return zero16;
-        return &DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) * cs.Cout + co];
-      }
-    }
-  };
-  auto b_src = [&](int kk0, int rl, int kk) -> const T* {
-    int gn = n0 + rl, gk = kk0 + kk;
-    if (gn >= cs.Cin || gk >= K) return zero16;
-    int64_t col = gk;
-    if constexpr (S2) {
-      int co = imod<POW2>(gk, cs.d_cout);
-      int kidx = idiv<POW2>(gk, cs.d_cout);
-      int kwi = kidx & (nkw - 1);
-      int khi = nkw == 2 ? (kidx >> 1) : kidx;
-      col = (int64_t)((start_h + 2 * khi) * cs.KW + start_w + 2 * kwi) *
-                cs.Cout + co;
-    }
-    return &WT2D[(int64_t)gn * KFULL + col];
-  };
-  auto stage = [&](int t, int which) {
-    int kk0 = t * BK;
-    glds_stage<T, BM>(As[which], wc,
-                      [&](int rl, int kk) { return a_src(kk0, rl, kk); });
-    glds_stage<T, BN>(Bs[which], wc,
-                      [&](int rl, int kk) { return b_src(kk0, rl, kk); });
-  };
-  constexpr int NPER = glds_count<T, BM>() + glds_count<T, BN>();
-
-  const int nch = (K + BK - 1) / BK;
-  stage(0, 0);
-  for (int t = 0; t < nch; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < nch) {
-      stage(t + 1, cur ^ 1);
-      wait_vmcnt<NPER>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    mfma_compute_tile(As[cur], Bs[cur], wc, acc);
-    __builtin_amdgcn_s_barrier();
-  }
+  // one LDS object per buffer, named statically in the 2x-unrolled k-loop
+  __shared__ alignas(16) T As0[BM * BK], As1[BM * BK];
+  __shared__ alignas(16) T Bs0[BN * BK], Bs1[BN * BK];
+  conv_db_kloop<true>(
+      As0, As1, Bs0, Bs1, wc, acc, DY, cs.d_ow.lg, cs.d_cout.lg, WT2D,
+      (int64_t)KFULL, cs.Cin, m0, n0, K, zero16,
+      // d_hw / d_w hold the per-class (Hc*Wc, Wc) divisors under S2
+      [&](int gm, int64_t& noff, int& p, int& q) {
+        const int n = gm >> cs.d_hw.lg;
+        const int rem = gm & (Hc * Wc - 1);
+        int ih = rem >> cs.d_w.lg, iw = rem & (Wc - 1);
+        if constexpr (S2) {
+          // th = ih + PH - kh is even by construction: oh = p - khi
+          p = (2 * ih + cls_a + cs.PH - start_h) >> 1;
+          q = (2 * iw + cls_b + cs.PW - start_w) >> 1;
+        } else {
+          p = ih + cs.PH;
+          q = iw + cs.PW;
+        }
+        noff = (int64_t)n << (cs.d_ohow.lg + cs.d_cout.lg);
+        return gm < M;
+      },
+      [&](int gk, int& dh, int& dw, int& c, int& bcol) {
+        const int kidx = gk >> cs.d_cout.lg;
+        c = gk & (cs.Cout - 1);
+        if constexpr (S2) {
+          // compacted (khi,kwi,co) -> full (kh*KW+kw)*Cout+co column
+          const int kwi = kidx & (nkw - 1);              // nkw is 1 or 2
+          const int khi = nkw == 2 ? (kidx >> 1) : kidx;
+          dh = khi;
+          dw = kwi;
+          bcol = (((start_h + 2 * khi) * cs.KW + start_w + 2 * kwi)
+                  << cs.d_cout.lg) + c;
+        } else {
+          kdecode(kidx, cs, dh, dw);
+          bcol = gk;
+        }
+      },
+      [&](int p, int q, int dh, int dw, int& oh, int& ow) {
+        const int th = p - dh, tw = q - dw;
+        if constexpr (S2 || S1) {
+          oh = th;
+          ow = tw;
+          return (unsigned)oh < (unsigned)cs.OH &&
+                 (unsigned)ow < (unsigned)cs.OW;
+        } else {
+          oh = th / cs.SH;
+          ow = tw / cs.SW;
+          return th >= 0 && tw >= 0 && oh * cs.SH == th &&
+                 ow * cs.SW == tw && oh < cs.OH && ow < cs.OW;
+        }
+      });
 
   epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
     if (row < M && col < cs.Cin) {
@@ -1105,22 +1241,28 @@ static bool all_pow2(const ConvShape& cs) {
          cs.d_hw.lg >= 0 && cs.d_w.lg >= 0 && cs.d_cout.lg >= 0;
 }
 
+// k-loop length up to which the double buffer is used (TNN_DB_MAXK, read
+// once). Past it bf16 takes the single-buffer form of the same DMA-staged
+// tile; fp32 falls back to k_conv_fwd.
+static int fwd_db_maxk() {
+  static const int maxk = []() {
+    const char* e = getenv("TNN_DB_MAXK");
+    return e ? atoi(e) : 2304;
+  }();
+  return maxk;
+}
+
+// true: the launcher wants the [Cout][K] weight and takes a DMA-staged
+// kernel, which also carries the fused statistics epilogue
 bool conv2d_fwd_wants_db(DT dt, const void* x, const ConvShape& cs) {
   static const bool db_on = []() {
     const char* e = getenv("TNN_FWD_DB");
     return !(e && atoi(e) == 0);
   }();
   if (!db_on) return false;
-  static const int maxk = []() {
-    const char* e = getenv("TNN_DB_MAXK");
-    return e ? atoi(e) : 2304;
-  }();
   int v = dt == DT::F32 ? 4 : 8;
-  // 2x LDS buffers cap occupancy at 3 blocks/CU: a win while the k-loop is
-  // short (measured +8% at K<=1152, -15% at K=4608 where the single-buffer
-  // kernel's 6 resident blocks hide latency better)
-  return cs.KH * cs.KW * cs.Cin <= maxk && all_pow2(cs) &&
-         cs.Cin % v == 0 && (((uintptr_t)x & 15) == 0);
+  if (dt == DT::F32 && cs.KH * cs.KW * cs.Cin > fwd_db_maxk()) return false;
+  return all_pow2(cs) && cs.Cin % v == 0 && (((uintptr_t)x & 15) == 0);
 }
 
 void transpose_w_fwd_launch(DT dt, const void* w, void* w_t2, int KHW, int Cin,
@@ -1163,6 +1305,13 @@ void conv2d_fwd_launch(DT dt, const void* x, const void* w, const void* w_t2,
                        (const float*)nullptr, (float*)y, (const float*)zero16,
                        cs, act);
   } else {
+    if (w_t2 && cs.KH * cs.KW * cs.Cin > fwd_db_maxk()) {
+      auto kern = stats ? k_conv_fwd_sb<true> : k_conv_fwd_sb<false>;
+      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const bf16*)x,
+                         (const bf16*)w_t2, (const bf16*)bias, (bf16*)y,
+                         (const bf16*)zero16, cs, act, stats);
+      return;
+    }
     if (w_t2) {
       auto kern = stats ? k_conv_fwd_db<bf16, true, true>
                         : k_conv_fwd_db<bf16, true>;

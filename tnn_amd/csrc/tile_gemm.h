@@ -215,6 +215,97 @@ DEV void mfma_compute_tile(const float* As, const float* Bs, const WaveCoord& w,
   }
 }
 
+// ---- row-major bf16 fragments the compiler does not fence -----------------
+// Same fragments as mfma_compute_tile(bf16), read with asm-issued
+// ds_read_b128 for double-buffered loops: before an LDS read it knows of,
+// the compiler drains every in-flight LDS-DMA it cannot prove disjoint
+// (s_waitcnt vmcnt(0) right after the barrier), which waits for the chunk
+// that was issued a few instructions earlier and serialises the loop (see
+// tr_frag_issue below for the k-major counterpart). What it cannot see it
+// does not wait for, so the caller owns the wait too: issue all fragments
+// of a k-step, then rm_frags_wait(). Every fragment read of a chunk has
+// then completed before the MFMAs that precede the buffer's freeing barrier.
+// An RmFrag holds an asm output register whose data has not landed yet:
+// between rm_frag_issue and rm_frags_wait it must not be read, moved or
+// copied (keep the fragments in a local array of the issuing function, as
+// mfma_compute_tile_nofence does); only get() after the wait is safe.
+struct RmFrag {
+  s16x8 v;
+  DEV bf16x8 get() const { return __builtin_bit_cast(bf16x8, v); }
+};
+
+// fragment rows row0..row0+15, k-columns k0..k0+31 of the swizzled
+// [rows][BK] image (lds_off)
+DEV RmFrag rm_frag_issue(const bf16* img, int row0, int k0, int lane) {
+  typedef __attribute__((address_space(3))) const char* lds_p;
+  const unsigned base = (unsigned)(size_t)(lds_p)(const char*)img;
+  const int off = lds_off<bf16>(row0 + (lane & 15), k0 + (lane >> 4) * 8);
+  RmFrag f;
+  asm volatile("ds_read_b128 %0, %1"
+               : "=v"(f.v) : "v"(base + 2u * (unsigned)off) : "memory");
+  return f;
+}
+
+// lgkmcnt(0) for the fragments of one k-step; the "+v" operands tie every
+// fragment to the wait, so no MFMA that consumes one is scheduled above it
+DEV void rm_frags_wait(RmFrag (&a)[FM], RmFrag (&b)[FN]) {
+  static_assert(FM == 4 && FN == 2, "operand list below");
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+v"(a[0].v), "+v"(a[1].v), "+v"(a[2].v), "+v"(a[3].v),
+                 "+v"(b[0].v), "+v"(b[1].v)
+               :: "memory");
+}
+
+// acc += A_tile * B_tile^T-stored: chunk order, k-steps and MFMA sequence of
+// mfma_compute_tile(bf16), so the accumulators come out bitwise the same
+DEV void mfma_compute_tile_nofence(const bf16* As, const bf16* Bs,
+                                   const WaveCoord& w, f32x4 acc[FM][FN]) {
+#pragma unroll
+  for (int ks = 0; ks < BK / 32; ++ks) {
+    RmFrag a[FM], b[FN];
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+      a[fm] = rm_frag_issue(As, w.wrow0 + fm * 16, ks * 32, w.lane);
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn)
+      b[fn] = rm_frag_issue(Bs, w.wcol0 + fn * 16, ks * 32, w.lane);
+    rm_frags_wait(a, b);
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+        acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a[fm].get(), b[fn].get(), acc[fm][fn], 0, 0, 0);
+  }
+}
+
+// ---- hoistable LDS-DMA staging of a [ROWS][BK] image -----------------------
+// glds_stage with the lane's slot made explicit: instruction i of the wave
+// fills 1 KiB region j = wid*NPW + i, where this lane's 16 bytes are tile
+// row glds_row(j, lane), k-columns glds_kk(j, lane) onward. Neither changes
+// from chunk to chunk, so callers decode the row once before the k-loop.
+template <typename T>
+DEV int glds_row(int j, int lane) {
+  constexpr int ROWB = BK * (int)sizeof(T);   // bytes per image row
+  return (1024 / ROWB) * j + lane / (ROWB / 16);
+}
+template <typename T>
+DEV int glds_kk(int j, int lane) {
+  constexpr int LPR = BK * (int)sizeof(T) / 16;   // lanes per row
+  const int rl = glds_row<T>(j, lane);
+  const int byte = ((lane % LPR) * 16) ^ ((((rl >> 3) ^ rl) & 7) << 4);
+  return byte / (int)sizeof(T);                   // lds_off's swizzle
+}
+// j must be wave-uniform (the DMA's LDS base is a scalar operand)
+template <typename T>
+DEV void glds_issue(T* img, int j, const T* src) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) unsigned int*)src,
+      (__attribute__((address_space(3))) unsigned int*)
+          &img[j * (1024 / (int)sizeof(T))],
+      16, 0, 0);
+}
+
 // ---- k-major bf16 images + transposed fragment reads (gfx950) -------------
 // A TN product (wgrad: both operands lie k-major in memory, [k][row]) needs
 // no transpose on the way INTO LDS: the image keeps the memory layout,
