@@ -16,7 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tnn_amd import models
 from tnn_amd.nn import CrossEntropyLoss, AdamW
 from tnn_amd.nn.layer import cast_compute_dtype
-from tnn_amd.models.generate import generate, generate_cached, generate_graphed
+from tnn_amd.models.generate import (generate, generate_batch,
+                                      generate_cached, generate_graphed)
 
 
 def main():
@@ -26,6 +27,9 @@ def main():
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--decode-tokens", type=int, default=32)
+    p.add_argument("--decode-batch", type=int, default=0,
+                   help="also time generate_batch over this many ragged "
+                        "prompts (greedy, one captured step for all rows)")
     p.add_argument("--train", action="store_true", default=True)
     p.add_argument("--graph", action="store_true",
                    help="also time the hipGraph-captured whole train step")
@@ -105,6 +109,20 @@ def main():
         dt = time.perf_counter() - t0
         n = len(out) - 16
         print(f"decode [{name}]: {n} tokens in {dt:.2f}s = {n / dt:.2f} tok/s")
+    if args.decode_batch > 0:
+        prompts = [list(range(b, b + 9 + (7 * b) % 16))
+                   for b in range(args.decode_batch)]
+        for i in range(2):   # the second call is the steady-state figure
+            t0 = time.perf_counter()
+            outs = generate_batch(model, prompts,
+                                  max_new_tokens=args.decode_tokens,
+                                  seq_len=args.seq_len, device=dev,
+                                  eot_token=None)
+            dt = time.perf_counter() - t0
+        n = sum(len(o) - len(q) for o, q in zip(outs, prompts))
+        print(f"decode [batched x{args.decode_batch}]: {n} tokens in "
+              f"{dt:.2f}s = {n / dt:.2f} tok/s aggregate, "
+              f"{n / dt / args.decode_batch:.2f} tok/s per sequence")
 
 
 if __name__ == "__main__":

@@ -172,10 +172,65 @@ def bench_decode():
            bytes_=2 * BH * cap * D * 2)
 
 
+def bench_skinny(dtype=torch.bfloat16):
+    """Batched-decode linears: the skinny route (ext.gemm_skinny) against
+    the general path the same rows take with TNN_SKINNY=0 (ext.gemm),
+    alternated in one session, next to the M=1 GEMV of the same weights.
+    Each call streams a different copy of the weights (a ring larger than
+    the caches would be the decode loop's regime; the ring here is capped
+    at 64 copies / 512 MB)."""
+    es = torch.empty(0, dtype=dtype).element_size()
+    for K, N in [(768, 2304), (768, 3072), (3072, 768), (768, 50257)]:
+        wbytes = K * N * es
+        ncopy = max(2, min(64, (512 << 20) // wbytes))
+        ws = [torch.randn(K, N, dtype=dtype, device=DEV) * 0.05
+              for _ in range(ncopy)]
+        b = torch.randn(N, dtype=dtype, device=DEV)
+        it = [0]
+
+        def nxt():
+            it[0] = (it[0] + 1) % ncopy
+            return ws[it[0]]
+
+        x1 = torch.randn(1, K, dtype=dtype, device=DEV)
+        t1 = min(timeit(lambda: ext.gemm(x1, nxt(), b, 0), iters=100)
+                 for _ in range(3))
+        report("gemv_m1", f"M1 K{K} N{N}", t1, bytes_=wbytes)
+        for M in (2, 4, 8, 16):
+            x = torch.randn(M, K, dtype=dtype, device=DEV)
+            ts, tg = [], []
+            for _ in range(3):   # alternate the two routes
+                ts.append(timeit(lambda: ext.gemm_skinny(x, nxt(), b, 0),
+                                 iters=100))
+                tg.append(timeit(lambda: ext.gemm(x, nxt(), b, 0),
+                                 iters=100))
+            report("gemm_skinny", f"M{M} K{K} N{N}", min(ts), bytes_=wbytes)
+            report("gemm_general", f"M{M} K{K} N{N}", min(tg), bytes_=wbytes)
+            print(f"{'':18s} skinny/M1 = {min(ts) / t1:.2f}x   "
+                  f"general/skinny = {min(tg) / min(ts):.2f}x")
+        del ws
+
+
+def bench_sample():
+    R, V = 16, 50257
+    logits = (torch.randn(R, V, device=DEV) * 2).to(torch.bfloat16)
+    step = torch.zeros(1, dtype=torch.int64, device=DEV)
+    for name, t, k, p in [("greedy", 0.0, 0, 1.0), ("temperature", 0.8, 0, 1.0),
+                          ("top_k=50", 0.8, 50, 1.0), ("top_p=0.95", 0.8, 0, 0.95),
+                          ("top_k=50 top_p=0.95", 0.8, 50, 0.95)]:
+        secs = timeit(lambda: ext.sample_logits(logits, t, k, p, 0, step),
+                      iters=200)
+        report("sample_logits", f"R{R} V{V} {name}", secs,
+               bytes_=logits.numel() * 2)
+    secs = timeit(lambda: logits.argmax(-1), iters=200)
+    report("torch argmax", f"R{R} V{V}", secs, bytes_=logits.numel() * 2)
+
+
 ALL = {"gemm": bench_gemm, "conv": bench_conv, "bn": bench_bn,
        "colsum": bench_colsum, "ce": bench_ce, "attn": bench_attn,
        "bmm": bench_bmm, "softmax": bench_softmax, "ln": bench_ln,
-       "gn": bench_gn, "decode": bench_decode}
+       "gn": bench_gn, "decode": bench_decode, "skinny": bench_skinny,
+       "sample": bench_sample}
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(ALL)

@@ -4,6 +4,12 @@
     python examples/gpt2_inference.py --model flash_gpt2_small \
         [--vocab vocab.bin] [--snapshot path] --prompt "Hello"
 
+    python examples/gpt2_inference.py --bf16 --batch 8 --top-k 50 --top-p 0.95
+
+``--batch N`` decodes N prompts together through ``generate_batch`` (one
+hipGraph-captured step for all rows on GPU); ``--top-k`` / ``--top-p`` /
+``--temperature`` / ``--seed`` switch it from greedy to on-device sampling.
+
 Without a vocab/snapshot this runs with random weights and raw token ids —
 the compute path (embedding -> N gpt blocks -> ln_f -> head, full-sequence
 recompute per token, matching the reference's no-KV-cache loop).
@@ -20,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tnn_amd import models
 from tnn_amd.data import Tokenizer
-from tnn_amd.models.generate import generate, generate_cached
+from tnn_amd.models.generate import generate, generate_batch, generate_cached
 from tnn_amd.nn.layer import cast_compute_dtype
 from tnn_amd.utils.checkpoint import load_model
 
@@ -36,6 +42,12 @@ def main():
     p.add_argument("--bf16", action="store_true")
     p.add_argument("--kv-cache", action="store_true",
                    help="cached decode (the reference recomputes)")
+    p.add_argument("--batch", type=int, default=0,
+                   help="decode this many prompts together (generate_batch)")
+    p.add_argument("--top-k", type=int, default=0)
+    p.add_argument("--top-p", type=float, default=1.0)
+    p.add_argument("--temperature", type=float, default=1.0)
+    p.add_argument("--seed", type=int, default=0)
     args = p.parse_args()
 
     model = (load_model(args.snapshot) if args.snapshot
@@ -47,6 +59,27 @@ def main():
 
     tok = Tokenizer().load(args.vocab) if args.vocab else None
     prompt_ids = tok.encode(args.prompt) if tok else list(range(10))
+
+    sampled = (args.top_k > 0 or args.top_p < 1.0 or args.temperature != 1.0)
+    if args.batch > 0 or sampled:
+        # the same prompt with a ragged tail of extra tokens per row
+        n = max(args.batch, 1)
+        prompts = [prompt_ids + prompt_ids[:b % len(prompt_ids)]
+                   for b in range(n)]
+        t0 = time.perf_counter()
+        outs = generate_batch(model, prompts, max_new_tokens=args.tokens,
+                              seq_len=args.seq_len, device=dev,
+                              eot_token=50256 if tok else None,
+                              greedy=not sampled,
+                              temperature=args.temperature, top_k=args.top_k,
+                              top_p=args.top_p, seed=args.seed)
+        dt = time.perf_counter() - t0
+        n_new = sum(len(o) - len(q) for o, q in zip(outs, prompts))
+        print(f"{n_new} tokens in {dt:.2f}s ({n_new / dt:.2f} tok/s aggregate "
+              f"over {n} sequences, {'sampled' if sampled else 'greedy'})")
+        for o in outs:
+            print(tok.decode(o) if tok else o)
+        return
 
     gen = generate_cached if args.kv_cache else generate
     t0 = time.perf_counter()

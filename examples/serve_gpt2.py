@@ -9,8 +9,18 @@ FastAPI server with:
   POST /generate            {"ids": [...]} or {"text": "..."} (needs vocab)
                             -> {"ids": [...], "text": ...,
                                 "tokens_per_s": float}
+  POST /generate_batch      {"prompts": [[...], ...], "max_new_tokens",
+                             "greedy", "temperature", "top_k", "top_p",
+                             "seed"}
+                            -> {"ids": [[...]], "new_ids": [[...]],
+                                "tokens_per_s": float}
 
-Decode runs the hipGraph-captured GPU-resident path on MI355X
+/generate_batch decodes ragged prompts together (models/generate.
+generate_batch: one captured step over all rows, weights streamed once per
+step for the whole batch, temperature / top-k / top-p sampled on the
+device), on GPU and CPU alike.
+
+/generate runs the hipGraph-captured GPU-resident path on MI355X
 (models/generate.generate_graphed: merged-QKV GEMV, fused decode
 attention — ~1,050 tok/s for GPT-2-small) and the eager KV-cache path on
 CPU. One request at a time (the KV cache is per-model state); a
@@ -34,7 +44,8 @@ from pydantic import BaseModel
 
 from tnn_amd import models
 from tnn_amd.nn.layer import cast_compute_dtype
-from tnn_amd.models.generate import generate_cached, generate_graphed
+from tnn_amd.models.generate import (generate_batch, generate_cached,
+                                      generate_graphed)
 
 
 class GenerateRequest(BaseModel):
@@ -43,6 +54,16 @@ class GenerateRequest(BaseModel):
     max_new_tokens: int = 64
     greedy: bool = True
     temperature: float = 1.0
+
+
+class GenerateBatchRequest(BaseModel):
+    prompts: List[List[int]]
+    max_new_tokens: int = 64
+    greedy: bool = True
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
 
 
 def build_app(model_name: str = "flash_gpt2_small",
@@ -103,6 +124,34 @@ def build_app(model_name: str = "flash_gpt2_small",
         return {"ids": out, "new_ids": new,
                 "text": tokenizer.decode(out) if tokenizer else None,
                 "tokens_per_s": round(len(new) / max(dt, 1e-9), 1)}
+
+    @app.post("/generate_batch")
+    def generate_batch_ep(req: GenerateBatchRequest):
+        prompts = [list(p) for p in req.prompts]
+        if not prompts:
+            raise HTTPException(400, "provide at least one prompt")
+        if any(not p or any(i < 0 for i in p) for p in prompts):
+            raise HTTPException(
+                400, "prompts must be non-empty lists of non-negative ints")
+        if req.max_new_tokens < 0:
+            raise HTTPException(400, "max_new_tokens must be >= 0")
+        with lock:
+            t0 = time.perf_counter()
+            try:
+                outs = generate_batch(model, prompts,
+                                      max_new_tokens=req.max_new_tokens,
+                                      seq_len=seq_len, device=dev,
+                                      greedy=req.greedy,
+                                      temperature=req.temperature,
+                                      top_k=req.top_k, top_p=req.top_p,
+                                      seed=req.seed)
+            except ValueError as e:
+                raise HTTPException(400, str(e))
+            dt = time.perf_counter() - t0
+        new = [o[len(p):] for o, p in zip(outs, prompts)]
+        n_new = sum(len(n) for n in new)
+        return {"ids": outs, "new_ids": new,
+                "tokens_per_s": round(n_new / max(dt, 1e-9), 1)}
 
     return app
 

@@ -248,6 +248,75 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
   return c;
 }
 
+// TNN_SKINNY=0 keeps ops.linear off the skinny route (A/B timing and an
+// escape hatch; read once per process)
+static bool skinny_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("TNN_SKINNY");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// y[M,N] = act(LN?(a)[M,K] @ b[K,N] + bias) + residual for M <= 16
+// (batched decode): every weight element is read once for all M rows.
+// A separate entry point, so ext.gemm keeps its numerics at tiny M.
+at::Tensor gemm_skinny(const at::Tensor& a, const at::Tensor& b,
+                       const c10::optional<at::Tensor>& bias, int64_t act_kind,
+                       const c10::optional<at::Tensor>& residual,
+                       const c10::optional<at::Tensor>& ln_gamma,
+                       const c10::optional<at::Tensor>& ln_beta,
+                       double ln_eps) {
+  CHECK_IN(a);
+  CHECK_IN(b);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(0),
+              "gemm_skinny shapes ", a.sizes(), " @ ", b.sizes());
+  TORCH_CHECK(a.scalar_type() == b.scalar_type(), "gemm_skinny dtype mismatch ",
+              a.scalar_type(), " vs ", b.scalar_type());
+  const DT dt = dt_of(a);  // fp32 / bf16 only
+  const int M = a.size(0), K = a.size(1), N = b.size(1);
+  TORCH_CHECK(M >= 1 && M <= SKINNY_MAX_M, "gemm_skinny wants 1 <= M <= ",
+              SKINNY_MAX_M, ", got M = ", M);
+  TORCH_CHECK(K >= 1 && N >= 1, "gemm_skinny: empty operand");
+  auto c = at::empty({M, N}, a.options());
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                bias->numel() == N && bias->scalar_type() == a.scalar_type(),
+                "gemm_skinny bias must be contiguous [", N, "] ",
+                a.scalar_type());
+    bp = bias->data_ptr();
+  }
+  const void* rp = nullptr;
+  if (residual.has_value()) {
+    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() &&
+                residual->scalar_type() == a.scalar_type() &&
+                residual->numel() == (int64_t)M * N,
+                "gemm_skinny residual mismatch");
+    rp = residual->data_ptr();
+  }
+  const float* lng = nullptr;
+  const float* lnb = nullptr;
+  if (ln_gamma.has_value()) {
+    TORCH_CHECK(ln_beta.has_value() && ln_gamma->is_cuda() &&
+                ln_beta->is_cuda() && ln_gamma->is_contiguous() &&
+                ln_beta->is_contiguous() &&
+                ln_gamma->scalar_type() == at::kFloat &&
+                ln_beta->scalar_type() == at::kFloat &&
+                ln_gamma->numel() == K && ln_beta->numel() == K,
+                "fused ln wants contiguous fp32 gamma/beta [", K, "]");
+    lng = ln_gamma->data_ptr<float>();
+    lnb = ln_beta->data_ptr<float>();
+  }
+  const int ns = gemm_skinny_nsplit(dt, M, N, K);
+  at::Tensor part;
+  float* pp = splitk_ws(part, a, ns, M, N);
+  gemm_skinny_launch(dt, a.data_ptr(), b.data_ptr(), bp, rp, c.data_ptr(), pp,
+                     ns, lng, lnb, (float)ln_eps, M, N, K, (int)act_kind,
+                     cur_stream());
+  return c;
+}
+
 at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& b) {
   // c[m, j] = sum_k a[m, k] * b[j, k]
   CHECK_IN(a);
@@ -1048,8 +1117,9 @@ at::Tensor smax_bwd(const at::Tensor& p, const at::Tensor& dy, double scale) {
 
 // ---- fused decode attention ------------------------------------------------
 // q [BH, D] bf16; k/v [BH, cap, D] bf16 full cache buffers. Either pos
-// (device int64 [1], len = pos+1 — graph-capturable) or len gives the
-// live KV length.
+// (device int64, len = pos+1 — graph-capturable) or len gives the live KV
+// length. pos holds one shared position, or B of them (BH % B == 0): row
+// bh then uses pos[bh / (BH / B)].
 at::Tensor attn_decode(const at::Tensor& q, const at::Tensor& k,
                        const at::Tensor& v,
                        const c10::optional<at::Tensor>& pos, int64_t len,
@@ -1065,21 +1135,100 @@ at::Tensor attn_decode(const at::Tensor& q, const at::Tensor& k,
   // bound; 12 heads x 1 split measured 22us/call): static from (BH, cap)
   // for hipGraph capture
   int splits = std::max<int>(1, std::min<int>(16, 256 / BH));
+  const int64_t* pos_ptr = nullptr;
+  int pos_div = 0;  // 0: one shared position
+  if (pos.has_value()) {
+    TORCH_CHECK(pos->scalar_type() == at::kLong && pos->is_cuda());
+    const int64_t nb = pos->numel();
+    if (nb != 1) {
+      TORCH_CHECK(nb >= 1 && pos->is_contiguous() && BH % nb == 0,
+                  "attn_decode pos must hold 1 or B positions with BH % B "
+                  "== 0, got ", nb, " for BH = ", BH);
+      pos_div = (int)(BH / nb);
+      // a batch brings B x heads rows, which the rule above would leave
+      // unsplit (192 rows at B=16: one block walks a whole sequence, 31 us
+      // per call); aim for ~4 blocks per CU instead. The shared-position
+      // form keeps its split counts, and so its numerics.
+      splits = std::max<int>(1, std::min<int>(16, 1024 / BH));
+    }
+    pos_ptr = pos->data_ptr<int64_t>();
+  }
   auto po = at::empty({(int64_t)BH * splits, D},
                       q.options().dtype(at::kFloat));
   auto ml = at::empty({(int64_t)BH * splits, 2},
                       q.options().dtype(at::kFloat));
   auto out = at::empty_like(q);
-  const int64_t* pos_ptr = nullptr;
-  if (pos.has_value()) {
-    TORCH_CHECK(pos->scalar_type() == at::kLong && pos->is_cuda());
-    pos_ptr = pos->data_ptr<int64_t>();
-  }
   attn_decode_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                      po.data_ptr<float>(), ml.data_ptr<float>(),
-                     out.data_ptr(), pos_ptr, (int)len, BH, cap, D, splits,
-                     (float)scale, cur_stream());
+                     out.data_ptr(), pos_ptr, pos_div, (int)len, BH, cap, D,
+                     splits, (float)scale, cur_stream());
   return out;
+}
+
+// One launch writes sequence b's new K and V rows at pos[b], all heads.
+// Caches [B,H,cap,D] contiguous; k_new / v_new [B,H,1,D] views with unit
+// stride along D (the merged-QKV projection's slices); pos [B] int64 on
+// device, trusted to be < cap.
+void kv_append(at::Tensor& k_cache, at::Tensor& v_cache,
+               const at::Tensor& k_new, const at::Tensor& v_new,
+               const at::Tensor& pos) {
+  CHECK_IN(k_cache);
+  CHECK_IN(v_cache);
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+              v_cache.scalar_type() == k_cache.scalar_type(),
+              "kv_append caches must be matching [B,H,cap,D]");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1),
+                cap = k_cache.size(2), D = k_cache.size(3);
+  for (const at::Tensor* t : {&k_new, &v_new}) {
+    TORCH_CHECK(t->is_cuda() && t->dim() == 4 && t->size(0) == B &&
+                t->size(1) == H && t->size(2) == 1 && t->size(3) == D &&
+                (D == 1 || t->stride(3) == 1) &&
+                t->scalar_type() == k_cache.scalar_type(),
+                "kv_append new rows must be [B,H,1,D] views of the cache "
+                "dtype with unit stride along D");
+  }
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong &&
+              pos.is_contiguous() && pos.numel() == B,
+              "kv_append pos must be int64 [B] on device");
+  kv_append_launch(dt_of(k_cache), k_cache.data_ptr(), v_cache.data_ptr(),
+                   k_new.data_ptr(), v_new.data_ptr(),
+                   pos.data_ptr<int64_t>(), (int)B, (int)H, (int)cap, (int)D,
+                   k_new.stride(0), k_new.stride(1), v_new.stride(0),
+                   v_new.stride(1), cur_stream());
+}
+
+// ---- on-device sampling ----------------------------------------------------
+// logits [R,V] bf16 -> ids [R] int64; step is a device int64 [1] (Philox
+// counter, advanced in-graph by the caller); u [R] fp32 overrides the RNG.
+at::Tensor sample_logits(const at::Tensor& logits, double temperature,
+                         int64_t top_k, double top_p, int64_t seed,
+                         const at::Tensor& step,
+                         const c10::optional<at::Tensor>& u) {
+  CHECK_IN(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.scalar_type() == at::kBFloat16,
+              "sample_logits wants bf16 [R,V] logits");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (int64_t)1 << 31, "sample_logits: bad V ", V);
+  TORCH_CHECK(temperature >= 0.0 && top_k >= 0 && top_p > 0.0 && top_p <= 1.0,
+              "sample_logits wants temperature >= 0, top_k >= 0, top_p in "
+              "(0, 1]");
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kLong &&
+              step.numel() == 1, "sample_logits step must be int64 [1]");
+  const float* up = nullptr;
+  if (u.has_value()) {
+    TORCH_CHECK(u->is_cuda() && u->is_contiguous() &&
+                u->scalar_type() == at::kFloat && u->numel() == R,
+                "sample_logits u must be fp32 [R] on device");
+    up = u->data_ptr<float>();
+  }
+  auto ids = at::empty({R}, logits.options().dtype(at::kLong));
+  if (R > 0)
+    sample_logits_launch(logits.data_ptr(), ids.data_ptr<int64_t>(), (int)R,
+                         (int)V, (float)temperature,
+                         (int)std::min<int64_t>(top_k, V), (float)top_p,
+                         (uint64_t)seed, step.data_ptr<int64_t>(), up,
+                         cur_stream());
+  return ids;
 }
 
 namespace imgcodec {
@@ -1102,6 +1251,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act_kind"), py::arg("residual") = c10::nullopt,
         py::arg("ln_gamma") = c10::nullopt, py::arg("ln_beta") = c10::nullopt,
         py::arg("ln_eps") = 1e-5);
+  m.def("gemm_skinny", &tnn::gemm_skinny, py::arg("a"), py::arg("b"),
+        py::arg("bias"), py::arg("act_kind"),
+        py::arg("residual") = c10::nullopt, py::arg("ln_gamma") = c10::nullopt,
+        py::arg("ln_beta") = c10::nullopt, py::arg("ln_eps") = 1e-5);
+  m.def("skinny_enabled", &tnn::skinny_enabled);
   m.def("gemm_nt", &tnn::gemm_nt);
   m.def("gemm_tn", &tnn::gemm_tn);
   m.def("mfma_selftest", &tnn::mfma_selftest);
@@ -1146,6 +1300,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("smax_fwd", &tnn::smax_fwd);
   m.def("smax_bwd", &tnn::smax_bwd);
   m.def("attn_decode", &tnn::attn_decode);
+  m.def("kv_append", &tnn::kv_append);
+  m.def("sample_logits", &tnn::sample_logits, py::arg("logits"),
+        py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("seed"), py::arg("step"), py::arg("u") = c10::nullopt);
   m.def("sgd_step", &tnn::sgd_step);
   m.def("adam_step", &tnn::adam_step, py::arg("param"), py::arg("master"),
         py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("step"),

@@ -7,7 +7,9 @@
 // Layout: q [BH, D] bf16; K/V caches [BH, cap, D] bf16 (full fixed-size
 // buffers). The live length comes either from a device int64 position
 // pointer (len = pos+1; hipGraph-capturable — the grid stays fixed while
-// the in-kernel range shrinks) or from a host int.
+// the in-kernel range shrinks) or from a host int. The pointer holds one
+// position shared by every row, or one per sequence (ragged batches):
+// row bh then reads pos[bh / heads_per_seq].
 //
 // Partial kernel: grid (BH, SPLITS), 256 threads. Per 256-wide KV tile:
 // each thread computes one dot(q, K[i]) (q cached in LDS, K rows read as
@@ -29,12 +31,15 @@ __global__ void k_attn_decode(const bf16* __restrict__ q,
                               const bf16* __restrict__ V,
                               float* __restrict__ po, float* __restrict__ ml,
                               const int64_t* __restrict__ pos_ptr,
-                              int len_static, int64_t skv, float scale) {
+                              int pos_div, int len_static, int64_t skv,
+                              float scale) {
   constexpr int NSUB = 256 / D;   // sub-accumulators per d column
   constexpr int PER = 256 / NSUB; // tile positions per sub
   const int bh = blockIdx.x;
   const int split = blockIdx.y, NS = gridDim.y;
-  const int len = pos_ptr ? (int)pos_ptr[0] + 1 : len_static;
+  // pos_div == 0: one shared position; else rows per sequence (BH / B)
+  const int len = pos_ptr ? (int)pos_ptr[pos_div ? bh / pos_div : 0] + 1
+                          : len_static;
   const int lo = (int)((int64_t)len * split / NS);
   const int hi = (int)((int64_t)len * (split + 1) / NS);
 
@@ -133,21 +138,58 @@ __global__ void k_attn_decode_fin(const float* __restrict__ po,
 
 void attn_decode_launch(const void* q, const void* k, const void* v, float* po,
                         float* ml, void* out, const int64_t* pos_ptr,
-                        int len_static, int BH, int cap, int D, int splits,
-                        float scale, hipStream_t s) {
+                        int pos_div, int len_static, int BH, int cap, int D,
+                        int splits, float scale, hipStream_t s) {
   dim3 pg(BH, splits);
   const int64_t skv = (int64_t)cap * D;
 #define L(DD)                                                                 \
   do {                                                                        \
     hipLaunchKernelGGL(k_attn_decode<DD>, pg, dim3(256), 0, s,                \
                        (const bf16*)q, (const bf16*)k, (const bf16*)v, po,    \
-                       ml, pos_ptr, len_static, skv, scale);                  \
+                       ml, pos_ptr, pos_div, len_static, skv, scale);         \
     hipLaunchKernelGGL(k_attn_decode_fin<DD>, dim3(BH), dim3(128), 0, s, po,  \
                        ml, (bf16*)out, splits);                               \
   } while (0)
   if (D == 64) L(64);
   else if (D == 128) L(128);
 #undef L
+}
+
+// Fused KV append for ragged batches: sequence b's new K and V rows (all
+// heads) land at cache position pos[b] in one launch. Caches are dense
+// [B,H,cap,D]; the new rows are the strided [B,H,1,D] views of the merged
+// QKV projection (element strides sb / sh, unit stride along D).
+// Positions are trusted to be < cap (the generation loop clamps them).
+template <typename T>
+__launch_bounds__(64)
+__global__ void k_kv_append(T* __restrict__ kc, T* __restrict__ vc,
+                            const T* __restrict__ kn, const T* __restrict__ vn,
+                            const int64_t* __restrict__ pos, int H, int cap,
+                            int D, int64_t k_sb, int64_t k_sh, int64_t v_sb,
+                            int64_t v_sh) {
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const int64_t dst = ((int64_t)blockIdx.x * cap + pos[b]) * D;
+  const T* ks = kn + b * k_sb + h * k_sh;
+  const T* vs = vn + b * v_sb + h * v_sh;
+  for (int d = threadIdx.x; d < D; d += 64) {
+    kc[dst + d] = ks[d];
+    vc[dst + d] = vs[d];
+  }
+}
+
+void kv_append_launch(DT dt, void* kc, void* vc, const void* kn,
+                      const void* vn, const int64_t* pos, int B, int H,
+                      int cap, int D, int64_t k_sb, int64_t k_sh, int64_t v_sb,
+                      int64_t v_sh, hipStream_t s) {
+  if (dt == DT::F32)
+    hipLaunchKernelGGL(k_kv_append<float>, dim3(B * H), dim3(64), 0, s,
+                       (float*)kc, (float*)vc, (const float*)kn,
+                       (const float*)vn, pos, H, cap, D, k_sb, k_sh, v_sb,
+                       v_sh);
+  else
+    hipLaunchKernelGGL(k_kv_append<bf16>, dim3(B * H), dim3(64), 0, s,
+                       (bf16*)kc, (bf16*)vc, (const bf16*)kn, (const bf16*)vn,
+                       pos, H, cap, D, k_sb, k_sh, v_sb, v_sh);
 }
 
 }  // namespace tnn

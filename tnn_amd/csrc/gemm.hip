@@ -685,6 +685,493 @@ void gemv_nn1_launch(DT dt, const void* x, const void* b, const void* bias,
   });
 }
 
+// ---------------------------------------------------------------------------
+// Skinny NN GEMM for batched decode, 2 <= M <= 16:
+//   y[M,N] = act(LN?(x)[M,K] @ B[K,N] + bias) + resid
+// Decode is weight-bandwidth-bound, so every B element is fetched once and
+// applied to all M rows: B streams straight into VGPRs (8-deep batched
+// loads, two columns per lane, no LDS round trip) while the block's
+// K-chunk of the M x rows sits in LDS as fp32 [k][MT] and is read back as
+// wave-uniform broadcasts. Blocks own 128 columns x one K slice (grid.y);
+// the block's 4 waves interleave the slice's k rows and fold through LDS.
+// With grid.y > 1 the block writes fp32 partials [split][M][N] and
+// k_skinny_fin folds them in a fixed order (deterministic, no atomics).
+// Any N and K: rows whose 2-column pairs cannot be loaded as one aligned
+// word (odd N) take the element-wise column mapping instead.
+// ---------------------------------------------------------------------------
+constexpr int SK_COLS = 128;  // columns per block
+constexpr int SK_KC = 512;    // k rows of x staged per LDS chunk
+constexpr int SK_U = 8;       // B loads in flight per lane
+
+// One lane's two B elements of row `off / N`. c0 / c1 are already
+// clamped into the row by the caller, so the loads are unconditional: a
+// load under a lane-dependent branch is waited for inside that branch,
+// which serialises the SK_U loads a batch is meant to keep in flight.
+template <typename T, bool VEC>
+DEV void sk_load(const T* __restrict__ B, int64_t off, int c0, int c1,
+                 float& w0, float& w1) {
+  if constexpr (VEC) {  // c0 even, N even: one aligned pair
+    struct alignas(2 * sizeof(T)) P2 { T e[2]; };
+    const P2 p = *(const P2*)&B[off + c0];
+    w0 = VecIO<T>::to_f32(p.e[0]);
+    w1 = VecIO<T>::to_f32(p.e[1]);
+  } else {
+    w0 = VecIO<T>::to_f32(B[off + c0]);
+    w1 = VecIO<T>::to_f32(B[off + c1]);
+  }
+}
+
+// one staged chunk: this wave's rows kk = wave, wave + 4, ... < kc_n
+template <typename T, int MT, bool VEC>
+DEV void sk_chunk(const T* __restrict__ B, const float* xs, int N, int kc0,
+                  int kc_n, int wave, int c0, int c1, float (&acc)[MT][2]) {
+  // columns past N read the row's last pair / element instead; their
+  // accumulators are never stored
+  c0 = min(c0, VEC ? N - 2 : N - 1);
+  c1 = min(c1, N - 1);
+  int kk = wave;
+  for (; kk + 4 * (SK_U - 1) < kc_n; kk += 4 * SK_U) {
+    float w0[SK_U], w1[SK_U];
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u)
+      sk_load<T, VEC>(B, (int64_t)(kc0 + kk + 4 * u) * N, c0, c1, w0[u],
+                      w1[u]);
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u) {
+      const float* xr = &xs[(kk + 4 * u) * MT];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        acc[m][0] += xr[m] * w0[u];
+        acc[m][1] += xr[m] * w1[u];
+      }
+    }
+  }
+  for (; kk < kc_n; kk += 4) {
+    float w0, w1;
+    sk_load<T, VEC>(B, (int64_t)(kc0 + kk) * N, c0, c1, w0, w1);
+    const float* xr = &xs[kk * MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      acc[m][0] += xr[m] * w0;
+      acc[m][1] += xr[m] * w1;
+    }
+  }
+}
+
+template <typename T, int MT>
+__launch_bounds__(256)
+__global__ void k_gemm_skinny(const T* __restrict__ x, const T* __restrict__ B,
+                              const T* __restrict__ bias,
+                              const T* __restrict__ res, T* __restrict__ y,
+                              float* __restrict__ part,
+                              const float* __restrict__ ln_g,
+                              const float* __restrict__ ln_b, float ln_eps,
+                              int M, int N, int K, int act_kind, int vec) {
+  constexpr int XS = SK_KC * MT;
+  constexpr int RED = 3 * MT * SK_COLS;
+  __shared__ alignas(16) float buf[XS > RED ? XS : RED];
+  __shared__ float mu_s[MT], is_s[MT];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * SK_COLS;
+  // accumulator j of this lane: adjacent columns (one aligned pair load)
+  // or lane-strided columns (element loads, wave-contiguous per j)
+  const int c0 = vec ? n0 + 2 * lane : n0 + lane;
+  const int c1 = vec ? c0 + 1 : c0 + 64;
+  const int nsplit = gridDim.y;
+  const int k_lo = (int)((int64_t)K * blockIdx.y / nsplit);
+  const int k_hi = (int)((int64_t)K * (blockIdx.y + 1) / nsplit);
+
+  if (ln_g) {
+    // per-row LayerNorm statistics over the full row (recomputed by every
+    // block, as in k_gemv_nn1): one wave per row
+    for (int m = wave; m < M; m += 4) {
+      float sm = 0.0f, sq = 0.0f;
+      for (int k = lane; k < K; k += 64) {
+        const float v = VecIO<T>::to_f32(x[(int64_t)m * K + k]);
+        sm += v;
+        sq += v * v;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        sm += __shfl_xor(sm, off, 64);
+        sq += __shfl_xor(sq, off, 64);
+      }
+      if (lane == 0) {
+        const float mean = sm / (float)K;
+        mu_s[m] = mean;
+        is_s[m] = rsqrtf(fmaxf(sq / (float)K - mean * mean, 0.0f) + ln_eps);
+      }
+    }
+    __syncthreads();
+  }
+
+  float acc[MT][2] = {};
+  for (int kc0 = k_lo; kc0 < k_hi; kc0 += SK_KC) {
+    const int kc_n = min(SK_KC, k_hi - kc0);
+    // stage x[0..MT)[kc0 .. kc0 + kc_n) as fp32 [k][MT]; rows >= M are zero
+    for (int i = threadIdx.x; i < kc_n * MT; i += 256) {
+      const int m = i / kc_n, kk = i - m * kc_n;
+      float v = 0.0f;
+      if (m < M) {
+        const int k = kc0 + kk;
+        v = VecIO<T>::to_f32(x[(int64_t)m * K + k]);
+        if (ln_g) v = (v - mu_s[m]) * is_s[m] * ln_g[k] + ln_b[k];
+      }
+      buf[kk * MT + m] = v;
+    }
+    __syncthreads();
+    if (vec)
+      sk_chunk<T, MT, true>(B, buf, N, kc0, kc_n, wave, c0, c1, acc);
+    else
+      sk_chunk<T, MT, false>(B, buf, N, kc0, kc_n, wave, c0, c1, acc);
+    __syncthreads();
+  }
+
+  // fold the 4 waves' k-interleaved partials (buf is free again)
+  if (wave > 0) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      buf[((wave - 1) * MT + m) * SK_COLS + lane] = acc[m][0];
+      buf[((wave - 1) * MT + m) * SK_COLS + 64 + lane] = acc[m][1];
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const Epilogue<T> ep{bias, res, N, act_kind};
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    if (m >= M) break;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int col = j ? c1 : c0;
+      if (col >= N) continue;
+      float a = acc[m][j];
+#pragma unroll
+      for (int w = 0; w < 3; ++w)
+        a += buf[(w * MT + m) * SK_COLS + j * 64 + lane];
+      if (part)
+        part[((int64_t)blockIdx.y * M + m) * N + col] = a;
+      else
+        y[(int64_t)m * N + col] = VecIO<T>::from_f32(ep(a, m, col));
+    }
+  }
+}
+
+// bf16, 4 < M <= 16: the same decomposition with the FMAs on the matrix
+// core. Sixteen scalar FMAs per weight element sit at the VALU ceiling at
+// HBM rate; v_mfma_f32_32x32x16_bf16 with the batch (zero-padded) as the
+// row dimension does them in passing. B is [K][N] but the MFMA B operand
+// wants 8 consecutive k per lane for ONE column, so each lane loads its
+// column pair from 8 consecutive rows -- straight to VGPRs, 32 lanes x
+// 4 B = one full 128-B line per row -- and regroups the 8 dwords in
+// registers (two 16-bit selects per
+// dword pair) into the operands of two MFMAs: one for the even columns of
+// the block, one for the odd ones. No LDS round trip and no transposed
+// weight copy. Odd N (rows not dword-aligned) loads single columns
+// instead; see the k loop. x is staged as bf16 [m][k] (rows padded 16 B against bank
+// conflicts; row 16 is zero and feeds the MFMA's unused rows 16..31), so
+// a fused LayerNorm's output is rounded to bf16 here, as the unfused
+// layer_norm -> gemm pair rounds it.
+constexpr int SKM_COLS = 64;    // columns per block
+constexpr int SKM_KC = 1024;    // k rows of x staged per LDS chunk
+
+// even N: the dword holding this lane's column pair, from 8 rows
+DEV void skm_load8(const bf16* __restrict__ B, int N, int r0, int r_max,
+                   int c0, unsigned (&d)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    // rows past the slice re-read its last row; x is zero there
+    d[j] = *(const unsigned*)&B[(int64_t)min(r0 + j, r_max) * N + c0];
+}
+
+// 8 rows of one lane -> the k-contiguous operands of its two columns
+DEV void skm_pack(const unsigned (&d)[8], bf16x8& b0, bf16x8& b1) {
+  int4v p0, p1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {  // dword = col c0 | col c0+1 << 16
+    p0[i] = (int)((d[2 * i] & 0xFFFFu) | (d[2 * i + 1] << 16));
+    p1[i] = (int)((d[2 * i] >> 16) | (d[2 * i + 1] & 0xFFFF0000u));
+  }
+  b0 = __builtin_bit_cast(bf16x8, p0);
+  b1 = __builtin_bit_cast(bf16x8, p1);
+}
+
+// odd N: rows are not dword-aligned, so a lane loads ONE column (n0 +
+// lane: 64 lanes x 2 B, wave-contiguous) from all 16 rows of a k step
+// and packs rows 0..7 and 8..15
+DEV void skm_load16(const bf16* __restrict__ B, int N, int r0, int r_max,
+                    int c, bf16x8& lo, bf16x8& hi) {
+  unsigned d[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    d[j] = *(const unsigned short*)&B[(int64_t)min(r0 + j, r_max) * N + c];
+  int4v p0, p1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    p0[i] = (int)(d[2 * i] | (d[2 * i + 1] << 16));
+    p1[i] = (int)(d[8 + 2 * i] | (d[9 + 2 * i] << 16));
+  }
+  lo = __builtin_bit_cast(bf16x8, p0);
+  hi = __builtin_bit_cast(bf16x8, p1);
+}
+
+template <bool VEC>
+__launch_bounds__(256)
+__global__ void k_gemm_skinny_mfma(const bf16* __restrict__ x,
+                                   const bf16* __restrict__ B,
+                                   const bf16* __restrict__ bias,
+                                   const bf16* __restrict__ res,
+                                   bf16* __restrict__ y,
+                                   float* __restrict__ part,
+                                   const float* __restrict__ ln_g,
+                                   const float* __restrict__ ln_b,
+                                   float ln_eps, int M, int N, int K,
+                                   int act_kind) {
+  constexpr int XLD = SKM_KC + 8;  // +16 B: rows land 4 banks apart
+  __shared__ alignas(16) bf16 xs[17 * XLD];
+  __shared__ float red[3 * 16 * 64];
+  __shared__ float mu_s[16], is_s[16];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int ci = lane & 31;  // column slot (MFMA B lane / output column)
+  const int kg = lane >> 5;  // which 8 of a 16-deep k step
+  const int n0 = blockIdx.x * SKM_COLS;
+  // output columns of the two MFMAs; loads clamp into the row
+  const int c0 = VEC ? n0 + 2 * ci : n0 + ci;
+  const int c1 = VEC ? c0 + 1 : c0 + 32;
+  // the column(s) this lane LOADS: its pair (even N), or n0 + lane (odd
+  // N; lanes 0-31 then hold the first MFMA's columns and lanes 32-63 the
+  // second's)
+  const int lc = VEC ? min(c0, N - 2) : min(n0 + lane, N - 1);
+  const int nsplit = gridDim.y;
+  const int k_lo = (int)((int64_t)K * blockIdx.y / nsplit);
+  const int k_hi = (int)((int64_t)K * (blockIdx.y + 1) / nsplit);
+
+  for (int i = threadIdx.x; i < XLD; i += 256) xs[16 * XLD + i] = f2bf(0.0f);
+  if (ln_g) {
+    for (int m = wave; m < M; m += 4) {
+      float sm = 0.0f, sq = 0.0f;
+      for (int k = lane; k < K; k += 64) {
+        const float v = bf2f(x[(int64_t)m * K + k]);
+        sm += v;
+        sq += v * v;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        sm += __shfl_xor(sm, off, 64);
+        sq += __shfl_xor(sq, off, 64);
+      }
+      if (lane == 0) {
+        const float mean = sm / (float)K;
+        mu_s[m] = mean;
+        is_s[m] = rsqrtf(fmaxf(sq / (float)K - mean * mean, 0.0f) + ln_eps);
+      }
+    }
+    __syncthreads();
+  }
+
+  f32x16 acc[2] = {};
+  const bf16* arow = &xs[(ci < 16 ? ci : 16) * XLD + kg * 8];
+  for (int kc0 = k_lo; kc0 < k_hi; kc0 += SKM_KC) {
+    const int kc_n = min(SKM_KC, k_hi - kc0);
+    const int kc16 = (kc_n + 15) & ~15;
+    // stage x[0..16)[kc0 .. kc0 + kc16) as bf16 [m][k], 8 elements per
+    // thread and step (one 16-B load where the source allows; element-wise
+    // staging serialised ~48 dependent 2-B loads per thread on the vocab
+    // head); rows >= M and k >= kc_n are zero
+    const int nk8 = kc16 / 8;
+    for (int i = threadIdx.x; i < 16 * nk8; i += 256) {
+      const int m = i / nk8, kk = (i - m * nk8) * 8;
+      float v[8] = {};
+      if (m < M) {
+        const int k = kc0 + kk;
+        const bf16* src = &x[(int64_t)m * K + k];
+        if (kk + 8 <= kc_n && aligned16(src)) {
+          const Pack16<bf16> p = *(const Pack16<bf16>*)src;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = bf2f(p.e[j]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (kk + j < kc_n) v[j] = bf2f(src[j]);
+        }
+        if (ln_g) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (kk + j < kc_n)
+              v[j] = (v[j] - mu_s[m]) * is_s[m] * ln_g[k + j] + ln_b[k + j];
+        }
+      }
+      Pack16<bf16> o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o.e[j] = f2bf(v[j]);
+      *(Pack16<bf16>*)&xs[m * XLD + kk] = o;
+    }
+    __syncthreads();
+    // this wave's 16-deep k steps: wave, wave + 4, ...
+    int ks = wave * 16;
+    if constexpr (VEC) {
+      // two steps per batch: 16 row loads in flight per lane
+      for (; ks + 64 < kc_n; ks += 128) {
+        unsigned d[8], e[8];
+        skm_load8(B, N, kc0 + ks + kg * 8, k_hi - 1, lc, d);
+        skm_load8(B, N, kc0 + ks + 64 + kg * 8, k_hi - 1, lc, e);
+        bf16x8 b0, b1;
+        const bf16x8 a0 = *(const bf16x8*)&arow[ks];
+        const bf16x8 a1 = *(const bf16x8*)&arow[ks + 64];
+        skm_pack(d, b0, b1);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[1], 0, 0, 0);
+        skm_pack(e, b0, b1);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1], 0, 0, 0);
+      }
+      for (; ks < kc_n; ks += 64) {
+        unsigned d[8];
+        skm_load8(B, N, kc0 + ks + kg * 8, k_hi - 1, lc, d);
+        bf16x8 b0, b1;
+        const bf16x8 a0 = *(const bf16x8*)&arow[ks];
+        skm_pack(d, b0, b1);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[1], 0, 0, 0);
+      }
+    } else {
+      // Each lane holds 16 rows of one column, but an MFMA wants both of
+      // its k halves (lanes 0-31 / 32-63) on the SAME 32 columns. So every
+      // MFMA here is 8 deep: both halves of the A operand read the same 8
+      // x values, and the B operand is zero in the half whose lanes hold
+      // the other MFMA's columns. Four MFMAs per step instead of two; the
+      // matrix core has the room.
+      const bf16x8 zero = {};
+      const bf16* arow8 = arow - kg * 8;
+      for (; ks < kc_n; ks += 64) {
+        bf16x8 lo, hi;
+        skm_load16(B, N, kc0 + ks, k_hi - 1, lc, lo, hi);
+        const bf16x8 a0 = *(const bf16x8*)&arow8[ks];
+        const bf16x8 a1 = *(const bf16x8*)&arow8[ks + 8];
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a0, kg == 0 ? lo : zero, acc[0], 0, 0, 0);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a1, kg == 0 ? hi : zero, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a0, kg == 1 ? lo : zero, acc[1], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a1, kg == 1 ? hi : zero, acc[1], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+
+  // C/D map of 32x32x16: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2)
+  // + 4 * (lane >> 5); rows < 16 live in regs 0..7. Fold the 4 waves.
+  if (wave > 0) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int r = 0; r < 8; ++r)
+        red[((wave - 1) * 16 + e * 8 + r) * 64 + lane] = acc[e][r];
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const Epilogue<bf16> ep{bias, res, N, act_kind};
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int col = e ? c1 : c0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int m = (r & 3) + 8 * (r >> 2) + 4 * kg;
+      if (m >= M || col >= N) continue;
+      float a = acc[e][r];
+#pragma unroll
+      for (int w = 0; w < 3; ++w) a += red[(w * 16 + e * 8 + r) * 64 + lane];
+      if (part)
+        part[((int64_t)blockIdx.y * M + m) * N + col] = a;
+      else
+        y[(int64_t)m * N + col] = f2bf(ep(a, m, col));
+    }
+  }
+}
+
+// fold the K-split partials [nsplit][M*N] in slab order + fused epilogue
+template <typename T>
+__launch_bounds__(256)
+__global__ void k_skinny_fin(const float* __restrict__ part,
+                             const T* __restrict__ bias,
+                             const T* __restrict__ res, T* __restrict__ y,
+                             int64_t mn, int N, int nsplit, int act_kind) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= mn) return;
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+  int s = 0;
+  for (; s + 4 <= nsplit; s += 4) {
+    a0 += part[(int64_t)s * mn + i];
+    a1 += part[(int64_t)(s + 1) * mn + i];
+    a2 += part[(int64_t)(s + 2) * mn + i];
+    a3 += part[(int64_t)(s + 3) * mn + i];
+  }
+  for (; s < nsplit; ++s) a0 += part[(int64_t)s * mn + i];
+  const float a = (a0 + a1) + (a2 + a3);
+  y[i] = VecIO<T>::from_f32(
+      Epilogue<T>{bias, res, N, act_kind}.at(a, (int)(i % N), i));
+}
+
+// bf16 rows past the plain-VALU form's comfort zone go to the MFMA kernel
+static bool skinny_use_mfma(DT dt, int M) { return dt == DT::BF16 && M > 4; }
+
+int gemm_skinny_nsplit(DT dt, int M, int N, int K) {
+  // fill the chip like gemv_nn1_nsplit: ~2 blocks per CU, slices >= 32 rows
+  const int ncb = ceil_div(N, skinny_use_mfma(dt, M) ? SKM_COLS : SK_COLS);
+  int ns = std::max(1, std::min(32, 512 / ncb));
+  ns = std::min(ns, std::max(1, K / 32));
+  return ns;
+}
+
+void gemm_skinny_launch(DT dt, const void* x, const void* b, const void* bias,
+                        const void* res, void* y, float* part, int nsplit,
+                        const float* ln_g, const float* ln_b, float ln_eps,
+                        int M, int N, int K, int act_kind, hipStream_t s) {
+  const int64_t mn = (int64_t)M * N;
+  if (skinny_use_mfma(dt, M)) {
+    dim3 g(ceil_div(N, SKM_COLS), nsplit);
+    const bool vec = N % 2 == 0 && ((uintptr_t)b % 4) == 0;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, g, dim3(256), 0, s, (const bf16*)x,
+                         (const bf16*)b, (const bf16*)bias, (const bf16*)res,
+                         (bf16*)y, nsplit > 1 ? part : nullptr, ln_g, ln_b,
+                         ln_eps, M, N, K, act_kind);
+    };
+    if (vec) launch(k_gemm_skinny_mfma<true>);
+    else launch(k_gemm_skinny_mfma<false>);
+    if (nsplit > 1)
+      hipLaunchKernelGGL(k_skinny_fin<bf16>,
+                         dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, s,
+                         part, (const bf16*)bias, (const bf16*)res, (bf16*)y,
+                         mn, N, nsplit, act_kind);
+    return;
+  }
+  dim3 g(ceil_div(N, SK_COLS), nsplit);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    // pair loads need even N (every row then starts pair-aligned)
+    const int vec = N % 2 == 0 && ((uintptr_t)b % (2 * sizeof(T))) == 0;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, g, dim3(256), 0, s, (const T*)x, (const T*)b,
+                         (const T*)bias, (const T*)res, (T*)y,
+                         nsplit > 1 ? part : nullptr, ln_g, ln_b, ln_eps, M, N,
+                         K, act_kind, vec);
+    };
+    if (M <= 2) launch(k_gemm_skinny<T, 2>);
+    else if (M <= 4) launch(k_gemm_skinny<T, 4>);
+    else if (M <= 8) launch(k_gemm_skinny<T, 8>);
+    else launch(k_gemm_skinny<T, 16>);
+    if (nsplit > 1)
+      hipLaunchKernelGGL(k_skinny_fin<T>, dim3((unsigned)((mn + 255) / 256)),
+                         dim3(256), 0, s, part, (const T*)bias, (const T*)res,
+                         (T*)y, mn, N, nsplit, act_kind);
+  });
+}
+
 // Legacy two-kernel K-split matvec (kept for K > GEMV1_MAX_K): fp32
 // partials then a finalize pass.
 template <typename T>

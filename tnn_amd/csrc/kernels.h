@@ -49,6 +49,13 @@ void gemv_nn1_launch(DT dt, const void* x, const void* b, const void* bias,
                      int K, int act_kind, hipStream_t s);
 // largest K of the single-launch M=1 matvec (its fp32 x cache in LDS)
 constexpr int GEMV1_MAX_K = 8192;
+// skinny GEMM (2 <= M <= 16): K-split count and launch
+constexpr int SKINNY_MAX_M = 16;
+int gemm_skinny_nsplit(DT dt, int M, int N, int K);
+void gemm_skinny_launch(DT dt, const void* x, const void* b, const void* bias,
+                        const void* res, void* y, float* part, int nsplit,
+                        const float* ln_g, const float* ln_b, float ln_eps,
+                        int M, int N, int K, int act_kind, hipStream_t s);
 void gemv_nn_launch(DT dt, const void* x, const void* b, const void* bias,
                     void* y, float* ws, int ks, int N, int K, int act_kind,
                     hipStream_t s);
@@ -255,8 +262,18 @@ void smax_bwd_launch(DT dt, const void* p, const void* dy, void* dx,
 // ---- decode.hip (bf16; D in {64,128}) --------------------------------------
 void attn_decode_launch(const void* q, const void* k, const void* v, float* po,
                         float* ml, void* out, const int64_t* pos_ptr,
-                        int len_static, int BH, int cap, int D, int splits,
-                        float scale, hipStream_t s);
+                        int pos_div, int len_static, int BH, int cap, int D,
+                        int splits, float scale, hipStream_t s);
+void kv_append_launch(DT dt, void* kc, void* vc, const void* kn,
+                      const void* vn, const int64_t* pos, int B, int H,
+                      int cap, int D, int64_t k_sb, int64_t k_sh, int64_t v_sb,
+                      int64_t v_sh, hipStream_t s);
+
+// ---- sample.hip (bf16 logits) ----------------------------------------------
+void sample_logits_launch(const void* logits, int64_t* ids, int R, int V,
+                          float temperature, int top_k, float top_p,
+                          uint64_t seed, const int64_t* step, const float* u,
+                          hipStream_t s);
 
 // ---- optim.hip -------------------------------------------------------------
 void sgd_step_launch(DT dt_p, const void* grad, DT dt_g, void* param,

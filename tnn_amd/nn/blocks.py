@@ -292,7 +292,10 @@ class _MHABase(Layer):
         device tensor ``pos_t`` ([1]), so a captured single-token step can
         be replayed with no host round-trips. Prefill (s>1) still runs the
         eager path; single-token steps write k/v at pos_t via index_copy_
-        and attend over the full capacity with a pos_t-derived mask."""
+        and attend over the full capacity with a pos_t-derived mask.
+        ``pos_t`` may also be ``[B]``, one position per sequence of a
+        ragged batch: the step then appends with ``ops.kv_append`` and
+        every sequence attends over its own length."""
         self._kv_cache = {"k": None, "v": None, "len": 0, "cap": max_len,
                           "pos_t": pos_t}
 
@@ -320,6 +323,10 @@ class _MHABase(Layer):
                 c["v"] = torch.zeros_like(c["k"])
             if "pos_t" in c and s == 1:
                 # graph-capturable single-token append at pos_t
+                if c["pos_t"].numel() > 1:   # one position per sequence
+                    ops.kv_append(c["k"], c["v"], k.detach(), v.detach(),
+                                  c["pos_t"])
+                    return q, c["k"], c["v"]
                 c["k"].index_copy_(2, c["pos_t"], k.detach())
                 c["v"].index_copy_(2, c["pos_t"], v.detach())
                 return q, c["k"], c["v"]
@@ -366,8 +373,12 @@ class _MHABase(Layer):
         if c is not None and "pos_t" in c and s_new == 1:
             if "arange" not in c:
                 c["arange"] = torch.arange(c["cap"], device=q.device)
-            scores = scores.masked_fill(c["arange"] > c["pos_t"],
-                                        float("-inf"))
+            if c["pos_t"].numel() > 1:   # [B, cap] -> over heads and the row
+                dead = (c["arange"][None, :]
+                        > c["pos_t"][:, None])[:, None, None, :]
+            else:
+                dead = c["arange"] > c["pos_t"]
+            scores = scores.masked_fill(dead, float("-inf"))
         elif self.causal and s_new > 1:
             pos_q = torch.arange(t - s_new, t, device=q.device).unsqueeze(-1)
             pos_k = torch.arange(t, device=q.device)

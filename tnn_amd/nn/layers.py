@@ -336,12 +336,17 @@ class PositionalEmbedding(Layer):
         self.weight = nn.Parameter(torch.randn(max_len, dim, dtype=dtype) * 0.02)
 
     _pos_offset = 0      # set by cached decode (models/generate.py)
-    _pos_tensor = None   # device int64 [1]: graph-capturable position
+    # device int64 [1], or [B] with one position per sequence (ragged
+    # batched decode): graph-capturable position
+    _pos_tensor = None
 
     def forward(self, x):
         s = x.shape[-2]
         if self._pos_tensor is not None and s == 1:
-            return x + self.weight.index_select(0, self._pos_tensor)
+            pe = self.weight.index_select(0, self._pos_tensor)
+            if self._pos_tensor.numel() > 1:
+                pe = pe.unsqueeze(1)   # [B, 1, D]: row b gets its own row
+            return x + pe
         off = self._pos_offset
         return x + self.weight[off:off + s]
 

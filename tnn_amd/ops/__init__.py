@@ -27,6 +27,8 @@ from .functional import (
     attention,
     sdpa_materialized,
     attention_decode,
+    kv_append,
+    sample_logits,
     scaled_softmax,
     group_norm,
     pointwise_loss,
@@ -49,6 +51,8 @@ __all__ = [
     "flash_attention_qkv",
     "sdpa_materialized",
     "attention_decode",
+    "kv_append",
+    "sample_logits",
     "scaled_softmax",
     "group_norm",
     "pointwise_loss",

@@ -427,9 +427,23 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     grad enabled act='relu' plus a residual is an error, other
     activations run unfused). ``ln=(gamma, beta, eps)``
     fuses a LayerNorm of x into the decode GEMV's staging (M=1,
-    inference only)."""
+    inference only). Under no_grad on GPU, 2 <= M <= 16 rows (batched
+    decode) take the skinny GEMM, which reads every weight once for all
+    rows and fuses ``ln`` too; ``TNN_SKINNY=0`` turns that route off."""
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
+    if (_use_hip(x) and 2 <= x2.shape[0] <= 16
+            and not torch.is_grad_enabled()
+            and x.dtype in (torch.float32, torch.bfloat16)
+            and _C.ext().skinny_enabled()):
+        gamma, beta, eps = ln if ln is not None else (None, None, 1e-5)
+        y = _C.ext().gemm_skinny(
+            x2.contiguous(), w.contiguous(),
+            None if bias is None else bias.contiguous(), ACT_KINDS[act],
+            residual.reshape(-1, residual.shape[-1]).contiguous()
+            if residual is not None else None,
+            gamma, beta, eps)
+        return y.reshape(*lead, w.shape[1])
     if ln is not None:
         gamma, beta, eps = ln
         if (_use_hip(x) and x2.shape[0] == 1
@@ -975,3 +989,111 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor,
     ext = _C.ext()
     return ext.attn_decode(q.contiguous(), k_cache, v_cache, pos,
                            length, scale)
+
+
+def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
+              k_new: torch.Tensor, v_new: torch.Tensor,
+              pos: torch.Tensor) -> None:
+    """Write sequence b's new K/V rows (``[B,H,1,D]``) into the
+    ``[B,H,cap,D]`` caches at ``pos[b]`` (int64 ``[B]``, each < cap), in
+    place: one fused launch on GPU, an index_put on CPU."""
+    if _use_hip(k_cache):
+        _C.ext().kv_append(k_cache, v_cache, k_new, v_new, pos)
+        return
+    rows = torch.arange(k_cache.shape[0], device=k_cache.device)
+    k_cache[rows, :, pos] = k_new[:, :, 0]
+    v_cache[rows, :, pos] = v_new[:, :, 0]
+
+
+# ---------------------------------------------------------------------------
+# sampling (temperature / top-k / top-p)
+# ---------------------------------------------------------------------------
+
+
+def _sample_rules(logits: torch.Tensor, temperature: float, top_k: int,
+                  top_p: float):
+    """The kept set and the unnormalised float64 weights exp(z - max) of
+    every row under the sampling rules of :func:`sample_logits` (weights
+    of dropped tokens are zero). Returns ``(keep [R,V] bool, w [R,V])``."""
+    z = logits.double() / temperature
+    V = z.shape[-1]
+    keep = torch.ones_like(z, dtype=torch.bool)
+    if 0 < top_k < V:
+        t_k = z.topk(top_k, dim=-1).values[..., -1:]
+        keep = z >= t_k
+    w = torch.exp(z - z.max(dim=-1, keepdim=True).values) * keep
+    if top_p < 1.0:
+        p = w / w.sum(-1, keepdim=True)
+        zs, order = z.sort(dim=-1, descending=True)
+        c = p.gather(-1, order).cumsum(-1)
+        # mass({z >= v}) is the running sum at the END of v's run of ties
+        last = torch.ones_like(keep)
+        last[..., :-1] = zs[..., :-1] != zs[..., 1:]
+        ok = last & (c >= top_p)
+        idx = torch.arange(V, device=z.device).expand_as(z)
+        first = torch.where(ok, idx, V - 1).min(-1, keepdim=True).values
+        t_p = zs.gather(-1, first)
+        keep = keep & (z >= t_p)
+        w = w * keep
+    return keep, w
+
+
+def sample_logits(logits: torch.Tensor, temperature: float = 1.0,
+                  top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                  step: Optional[torch.Tensor] = None,
+                  u: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sample one token id per row of ``logits [R,V]`` -> int64 ``[R]``.
+
+    1. ``z = logits / temperature``; ``temperature == 0`` or ``top_k == 1``
+       is greedy and returns the lowest index among the maxima.
+    2. ``top_k > 0`` keeps ``{z >= t_k}``, ``t_k`` the k-th largest value.
+       Ties at the threshold are all kept (bf16 logits tie constantly, and
+       this is the only scan-order-independent definition).
+    3. ``top_p < 1`` keeps, among the survivors with their renormalised
+       probabilities, ``{z >= t_p}`` where ``t_p`` is the largest value
+       with ``mass({z >= t_p}) >= top_p``; ties included again.
+    4. With ``u`` in (0, 1], return the first kept index in token order
+       whose running sum of kept ``exp(z - max)`` reaches ``u * total``
+       (the last kept index if rounding leaves none).
+
+    ``seed`` (host int) and ``step`` (int64 ``[1]`` tensor) select the
+    random number; the result is a pure function of the arguments. ``u``
+    (float ``[R]``) overrides the generator and exists for tests.
+
+    bf16 logits on GPU run the fused HIP kernel (Philox keyed by ``seed``
+    with counter ``(step, row)``; ``step`` lives on the device so a
+    captured graph draws fresh numbers each replay). Everything else runs
+    the float64 torch form of the same rules, drawing ``u`` from a
+    ``torch.Generator`` seeded by ``(seed, step)``. The two random
+    streams differ: the same seed gives different tokens on CPU and GPU.
+    """
+    if temperature < 0 or top_k < 0 or not (0.0 < top_p <= 1.0):
+        raise ValueError("sample_logits wants temperature >= 0, top_k >= 0 "
+                         "and top_p in (0, 1]")
+    assert logits.dim() == 2, "sample_logits wants [R, V] logits"
+    if _use_hip(logits) and logits.dtype == torch.bfloat16:
+        if step is None:
+            step = torch.zeros(1, dtype=torch.int64, device=logits.device)
+        return _C.ext().sample_logits(logits.contiguous(), float(temperature),
+                                      int(top_k), float(top_p), int(seed),
+                                      step, u)
+    R, V = logits.shape
+    idx = torch.arange(V, device=logits.device).expand(R, V)
+    if temperature == 0 or top_k == 1:
+        z = logits.double()
+        top = z == z.max(dim=-1, keepdim=True).values
+        return torch.where(top, idx, V).min(-1).values
+    keep, w = _sample_rules(logits, temperature, top_k, top_p)
+    if u is None:
+        st = 0 if step is None else int(step.reshape(-1)[0].item())
+        g = torch.Generator().manual_seed(
+            (int(seed) * 1000003 + st) % (2 ** 63))
+        # (0, 1], like the device generator
+        u = 1.0 - torch.rand(R, generator=g, dtype=torch.float64)
+    cdf = w.cumsum(-1)
+    target = u.to(device=logits.device, dtype=torch.float64).reshape(R, 1) \
+        * cdf[:, -1:]
+    hit = keep & (cdf >= target)
+    first = torch.where(hit, idx, V).min(-1).values
+    last_kept = torch.where(keep, idx, -1).max(-1).values
+    return torch.where(first < V, first, last_kept)
