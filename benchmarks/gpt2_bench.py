@@ -33,6 +33,9 @@ def main():
     p.add_argument("--train", action="store_true", default=True)
     p.add_argument("--graph", action="store_true",
                    help="also time the hipGraph-captured whole train step")
+    p.add_argument("--max-grad-norm", type=float, default=0.0,
+                   help="global-norm gradient clipping threshold of the "
+                        "train step (0 = off)")
     args = p.parse_args()
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -45,7 +48,8 @@ def main():
     if args.train and args.steps > 0:
         model.train()
         crit = CrossEntropyLoss()
-        opt = AdamW(model.parameters(), lr=1e-4)
+        opt = AdamW(model.parameters(), lr=1e-4,
+                    max_grad_norm=args.max_grad_norm)
         x = torch.randint(0, 50257, (args.batch, args.seq_len), device=dev)
         y = torch.randint(0, 50257, (args.batch, args.seq_len), device=dev)
 
@@ -77,6 +81,7 @@ def main():
                   f"loss {gloss.item():.3f})")
             gstep.sync_step_count()
             opt._step_dev = None  # eager steps resume host step counting
+            opt._lr_dev = None
             del gstep
 
         for _ in range(3):
@@ -91,6 +96,10 @@ def main():
         print(f"train: {args.model} bs={args.batch} seq={args.seq_len}: "
               f"{toks / dt:,.0f} tok/s ({dt / args.steps * 1e3:.1f} ms/step, "
               f"loss {loss.item():.3f})")
+        if args.max_grad_norm > 0:
+            print(f"clip: max_grad_norm={args.max_grad_norm} last grad norm "
+                  f"{opt.last_grad_norm.item():.3f}, skipped steps "
+                  f"{opt.skipped_steps()}")
 
 
 

@@ -226,11 +226,38 @@ def bench_sample():
     report("torch argmax", f"R{R} V{V}", secs, bytes_=logits.numel() * 2)
 
 
+def bench_gradnorm():
+    """Global gradient norm (k_gradsq_mt + k_clip_fin) at the GPT-2-small
+    gradient size: 124.4M elements split like the model's tensors (the
+    embedding, 12 blocks of attention/MLP matrices, the small vectors)."""
+    from tnn_amd.nn.optim import _GradNormWorkspace
+    shapes = [(50257, 768), (1024, 768)]
+    for _ in range(12):
+        shapes += [(768, 2304), (2304,), (768, 768), (768,), (768, 3072),
+                   (3072,), (3072, 768), (768,), (768,), (768,), (768,),
+                   (768,)]
+    shapes += [(768,), (768,)]
+    for dtype in (torch.bfloat16, torch.float32):
+        grads = [torch.randn(*s, device=DEV).to(dtype) for s in shapes]
+        n = sum(g.numel() for g in grads)
+        ws = _GradNormWorkspace()
+        dev = grads[0].device
+        # descriptors built once, as in a warmed-up optimizer step: the
+        # timed call is the two launches
+        recs = ws.loose_records(list(enumerate(grads)), dev)
+        secs = timeit(lambda: ws.run(ext, recs, dev, 1.0, count_skips=False),
+                      iters=200)
+        nbytes = n * grads[0].element_size()
+        shape = f"{len(grads)} tensors {n / 1e6:.1f}M {dtype}"
+        print(f"{'grad_global_norm':18s} {shape:42s} {secs * 1e3:8.3f} ms "
+              f"{nbytes / secs / 1e9:8.1f} GB/s")
+
+
 ALL = {"gemm": bench_gemm, "conv": bench_conv, "bn": bench_bn,
        "colsum": bench_colsum, "ce": bench_ce, "attn": bench_attn,
        "bmm": bench_bmm, "softmax": bench_softmax, "ln": bench_ln,
        "gn": bench_gn, "decode": bench_decode, "skinny": bench_skinny,
-       "sample": bench_sample}
+       "sample": bench_sample, "gradnorm": bench_gradnorm}
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(ALL)

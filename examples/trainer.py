@@ -35,11 +35,15 @@ def main():
     p.add_argument("--batch-size", type=int, default=None)
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--dtype", default="float32")
+    p.add_argument("--max-grad-norm", type=float, default=None,
+                   help="global-norm gradient clipping threshold (0 = off)")
     args = p.parse_args()
 
     overrides = {k: v for k, v in [("epochs", args.epochs),
                                    ("batch_size", args.batch_size),
-                                   ("learning_rate", args.lr)] if v is not None}
+                                   ("learning_rate", args.lr),
+                                   ("max_grad_norm", args.max_grad_norm)]
+                 if v is not None}
     cfg = (TrainingConfig.from_json(args.config, **overrides) if args.config
            else TrainingConfig.from_env(**overrides))
 
@@ -66,7 +70,8 @@ def main():
             args.dataset, path=args.data_path, train=False,
             batch_size=cfg.batch_size)
 
-    opt = AdamW(model.parameters(), lr=cfg.learning_rate)
+    opt = AdamW(model.parameters(), lr=cfg.learning_rate,
+                max_grad_norm=cfg.max_grad_norm)
     sched = schedulers.CosineAnnealingLR(opt, t_max=cfg.epochs)
     result = train_model(model, train_loader, val_loader, CrossEntropyLoss(),
                          opt, sched, cfg)

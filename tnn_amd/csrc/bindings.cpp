@@ -1016,9 +1016,28 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 }
 
 // ---- optimizers ------------------------------------------------------------
+// clip: the CLIP_STATE-float vector clip_finalize wrote; lr_dev: one float
+static const float* clip_ptr(const c10::optional<at::Tensor>& clip) {
+  if (!clip.has_value()) return nullptr;
+  TORCH_CHECK(clip->is_cuda() && clip->is_contiguous() &&
+                  clip->scalar_type() == at::kFloat &&
+                  clip->numel() >= CLIP_STATE,
+              "clip must be a contiguous fp32 GPU vector of ", (int)CLIP_STATE);
+  return clip->data_ptr<float>();
+}
+static const float* lr_ptr(const c10::optional<at::Tensor>& lr_dev) {
+  if (!lr_dev.has_value()) return nullptr;
+  TORCH_CHECK(lr_dev->is_cuda() && lr_dev->scalar_type() == at::kFloat &&
+                  lr_dev->numel() >= 1,
+              "lr_dev must be an fp32 GPU scalar");
+  return lr_dev->data_ptr<float>();
+}
+
 void sgd_step(at::Tensor param, at::Tensor master, const at::Tensor& grad,
               const c10::optional<at::Tensor>& momentum_buf, double lr,
-              double momentum, double weight_decay, bool nesterov) {
+              double momentum, double weight_decay, bool nesterov,
+              const c10::optional<at::Tensor>& clip = c10::nullopt,
+              const c10::optional<at::Tensor>& lr_dev = c10::nullopt) {
   CHECK_IN(param);
   bool has_master = master.data_ptr() != param.data_ptr();
   float* mb = momentum_buf.has_value() ? momentum_buf->data_ptr<float>()
@@ -1026,14 +1045,74 @@ void sgd_step(at::Tensor param, at::Tensor master, const at::Tensor& grad,
   sgd_step_launch(dt_of(param), grad.data_ptr(), dt_of(grad), param.data_ptr(),
                   master.data_ptr<float>(), mb, param.numel(), (float)lr,
                   (float)momentum, (float)weight_decay, nesterov, has_master,
-                  cur_stream());
+                  clip_ptr(clip), lr_ptr(lr_dev), cur_stream());
+}
+
+// Sum of squares of the gradients a descriptor lists: one fp32 partial per
+// chunk into part[base .. base + chunks.numel()). desc holds `stride` int64
+// per tensor, grad pointer in slot gslot, numel in slot nslot.
+void grad_sumsq_mt(const at::Tensor& desc, const at::Tensor& chunks,
+                   int64_t stride, int64_t gslot, int64_t nslot, int64_t dt_g,
+                   at::Tensor part, int64_t base) {
+  CHECK_IN(desc);
+  CHECK_IN(chunks);
+  CHECK_IN(part);
+  TORCH_CHECK(desc.scalar_type() == at::kLong &&
+                  chunks.scalar_type() == at::kLong &&
+                  part.scalar_type() == at::kFloat,
+              "grad_sumsq_mt: desc/chunks int64, part fp32");
+  TORCH_CHECK(stride > 0 && gslot >= 0 && gslot < stride && nslot >= 0 &&
+                  nslot < stride && desc.numel() % stride == 0,
+              "grad_sumsq_mt: bad descriptor layout");
+  TORCH_CHECK(dt_g == 0 || dt_g == 1, "grad_sumsq_mt: fp32/bf16 grads only");
+  TORCH_CHECK(base >= 0 && base + chunks.numel() <= part.numel(),
+              "grad_sumsq_mt: partial buffer too small");
+  grad_sumsq_mt_launch((DT)dt_g, desc.data_ptr<int64_t>(),
+                       chunks.data_ptr<int64_t>(), (int)chunks.numel(),
+                       (int)stride, (int)gslot, (int)nslot,
+                       part.data_ptr<float>() + base, cur_stream());
+}
+
+// Fold part[0 .. npart) in a fixed order (or take the already reduced
+// sumsq_in) and write {sumsq, norm, coef, skip} into state.
+void clip_finalize(const at::Tensor& part, int64_t npart, double max_norm,
+                   at::Tensor state,
+                   const c10::optional<at::Tensor>& skipped = c10::nullopt,
+                   const c10::optional<at::Tensor>& sumsq_in = c10::nullopt) {
+  CHECK_IN(part);
+  CHECK_IN(state);
+  TORCH_CHECK(part.scalar_type() == at::kFloat && npart >= 0 &&
+                  npart <= part.numel(),
+              "clip_finalize: part fp32 with at least npart elements");
+  TORCH_CHECK(state.scalar_type() == at::kFloat &&
+                  state.numel() >= CLIP_STATE,
+              "clip_finalize: state fp32 x ", (int)CLIP_STATE);
+  int64_t* sk = nullptr;
+  if (skipped.has_value()) {
+    TORCH_CHECK(skipped->is_cuda() && skipped->scalar_type() == at::kLong &&
+                    skipped->numel() >= 1,
+                "clip_finalize: skipped must be an int64 GPU scalar");
+    sk = skipped->data_ptr<int64_t>();
+  }
+  const float* sin = nullptr;
+  if (sumsq_in.has_value()) {
+    TORCH_CHECK(sumsq_in->is_cuda() && sumsq_in->scalar_type() == at::kFloat &&
+                    sumsq_in->numel() >= 1,
+                "clip_finalize: sumsq_in must be an fp32 GPU scalar");
+    sin = sumsq_in->data_ptr<float>();
+  }
+  clip_finalize_launch(part.data_ptr<float>(), (int)npart, sin,
+                       (float)max_norm, state.data_ptr<float>(), sk,
+                       cur_stream());
 }
 
 void adam_step(at::Tensor param, at::Tensor master, const at::Tensor& grad,
                at::Tensor m, at::Tensor v, int64_t step, double lr,
                double beta1, double beta2, double eps, double weight_decay,
                bool adamw,
-               const c10::optional<at::Tensor>& step_dev = c10::nullopt) {
+               const c10::optional<at::Tensor>& step_dev = c10::nullopt,
+               const c10::optional<at::Tensor>& clip = c10::nullopt,
+               const c10::optional<at::Tensor>& lr_dev = c10::nullopt) {
   CHECK_IN(param);
   bool has_master = master.data_ptr() != param.data_ptr();
   const int64_t* sd =
@@ -1042,14 +1121,17 @@ void adam_step(at::Tensor param, at::Tensor master, const at::Tensor& grad,
                    master.data_ptr<float>(), m.data_ptr<float>(),
                    v.data_ptr<float>(), param.numel(), (int)step, sd,
                    (float)lr, (float)beta1, (float)beta2, (float)eps,
-                   (float)weight_decay, adamw, has_master, cur_stream());
+                   (float)weight_decay, adamw, has_master, clip_ptr(clip),
+                   lr_ptr(lr_dev), cur_stream());
 }
 
 void adam_step_mt(const at::Tensor& desc, const at::Tensor& chunks,
                   int64_t dt_p, int64_t dt_g, bool has_master, int64_t step,
                   double lr, double beta1, double beta2, double eps,
                   double weight_decay, bool adamw,
-                  const c10::optional<at::Tensor>& step_dev = c10::nullopt) {
+                  const c10::optional<at::Tensor>& step_dev = c10::nullopt,
+                  const c10::optional<at::Tensor>& clip = c10::nullopt,
+                  const c10::optional<at::Tensor>& lr_dev = c10::nullopt) {
   CHECK_IN(desc);
   CHECK_IN(chunks);
   const int64_t* sd =
@@ -1058,7 +1140,7 @@ void adam_step_mt(const at::Tensor& desc, const at::Tensor& chunks,
                  desc.data_ptr<int64_t>(), chunks.data_ptr<int64_t>(),
                  (int)chunks.numel(), (int)step, sd, (float)lr, (float)beta1,
                  (float)beta2, (float)eps, (float)weight_decay, adamw,
-                 cur_stream());
+                 clip_ptr(clip), lr_ptr(lr_dev), cur_stream());
 }
 
 // ---- batched MFMA gemm -----------------------------------------------------
@@ -1304,17 +1386,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_logits", &tnn::sample_logits, py::arg("logits"),
         py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("step"), py::arg("u") = c10::nullopt);
-  m.def("sgd_step", &tnn::sgd_step);
+  m.def("sgd_step", &tnn::sgd_step, py::arg("param"), py::arg("master"),
+        py::arg("grad"), py::arg("momentum_buf"), py::arg("lr"),
+        py::arg("momentum"), py::arg("weight_decay"), py::arg("nesterov"),
+        py::arg("clip") = c10::nullopt, py::arg("lr_dev") = c10::nullopt);
   m.def("adam_step", &tnn::adam_step, py::arg("param"), py::arg("master"),
         py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("step"),
         py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
         py::arg("weight_decay"), py::arg("adamw"),
-        py::arg("step_dev") = c10::nullopt);
+        py::arg("step_dev") = c10::nullopt, py::arg("clip") = c10::nullopt,
+        py::arg("lr_dev") = c10::nullopt);
   m.def("adam_step_mt", &tnn::adam_step_mt, py::arg("desc"),
         py::arg("chunks"), py::arg("dt_p"), py::arg("dt_g"),
         py::arg("has_master"), py::arg("step"), py::arg("lr"),
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
         py::arg("weight_decay"), py::arg("adamw"),
-        py::arg("step_dev") = c10::nullopt);
+        py::arg("step_dev") = c10::nullopt, py::arg("clip") = c10::nullopt,
+        py::arg("lr_dev") = c10::nullopt);
+  m.def("grad_sumsq_mt", &tnn::grad_sumsq_mt, py::arg("desc"),
+        py::arg("chunks"), py::arg("stride"), py::arg("gslot"),
+        py::arg("nslot"), py::arg("dt_g"), py::arg("part"), py::arg("base"));
+  m.def("clip_finalize", &tnn::clip_finalize, py::arg("part"),
+        py::arg("npart"), py::arg("max_norm"), py::arg("state"),
+        py::arg("skipped") = c10::nullopt, py::arg("sumsq_in") = c10::nullopt);
   m.def("decode_image", &tnn::imgcodec::decode_image);
 }

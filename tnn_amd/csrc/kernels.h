@@ -276,19 +276,37 @@ void sample_logits_launch(const void* logits, int64_t* ids, int R, int V,
                           hipStream_t s);
 
 // ---- optim.hip -------------------------------------------------------------
+// Slots of the fp32 clip state vector k_clip_fin writes and the update
+// kernels read (`clip`): sum of squares, pre-clip global norm,
+// min(1, max_norm / (norm + 1e-6)), and 1.0 when the norm is not finite.
+enum ClipSlot : int {
+  CLIP_SUMSQ = 0, CLIP_NORM = 1, CLIP_COEF = 2, CLIP_SKIP = 3, CLIP_STATE = 4,
+};
+// `clip` and `lr_dev` are nullable device pointers; null = no clipping /
+// the by-value `lr`.
 void sgd_step_launch(DT dt_p, const void* grad, DT dt_g, void* param,
                      float* master, float* momentum_buf, int64_t n, float lr,
                      float momentum, float weight_decay, bool nesterov,
-                     bool has_master, hipStream_t s);
+                     bool has_master, const float* clip, const float* lr_dev,
+                     hipStream_t s);
 void adam_step_launch(DT dt_p, const void* grad, DT dt_g, void* param,
                       float* master, float* m, float* v, int64_t n, int step,
                       const int64_t* step_dev, float lr, float beta1,
                       float beta2, float eps, float weight_decay, bool adamw,
-                      bool has_master, hipStream_t s);
+                      bool has_master, const float* clip, const float* lr_dev,
+                      hipStream_t s);
 void adam_mt_launch(DT dt_p, DT dt_g, bool has_master, const int64_t* desc,
                     const int64_t* chunks, int nchunks, int step,
                     const int64_t* step_dev, float lr, float beta1,
                     float beta2, float eps, float weight_decay, bool adamw,
-                    hipStream_t s);
+                    const float* clip, const float* lr_dev, hipStream_t s);
+// one fp32 partial per chunk into part[0 .. nchunks)
+void grad_sumsq_mt_launch(DT dt_g, const int64_t* desc, const int64_t* chunks,
+                          int nchunks, int stride, int gslot, int nslot,
+                          float* part, hipStream_t s);
+// folds part[0 .. npart) (or takes *sumsq_in) into state[CLIP_STATE]
+void clip_finalize_launch(const float* part, int npart, const float* sumsq_in,
+                          float max_norm, float* state, int64_t* skipped,
+                          hipStream_t s);
 
 }  // namespace tnn

@@ -33,6 +33,7 @@ class TrainingConfig:
     epochs: int = 10
     batch_size: int = 128
     learning_rate: float = 1e-3
+    max_grad_norm: float = 0.0  # global-norm gradient clipping, 0 = off
     grad_accum_steps: int = 1
     num_microbatches: int = 4
     device: str = "cuda" if torch.cuda.is_available() else "cpu"
@@ -50,6 +51,7 @@ class TrainingConfig:
             epochs=get("NUM_EPOCHS", int, cls.epochs),
             batch_size=get("BATCH_SIZE", int, cls.batch_size),
             learning_rate=get("LEARNING_RATE", float, cls.learning_rate),
+            max_grad_norm=get("MAX_GRAD_NORM", float, cls.max_grad_norm),
             grad_accum_steps=get("GRAD_ACCUM_STEPS", int, cls.grad_accum_steps),
             num_microbatches=get("NUM_MICROBATCHES", int, cls.num_microbatches),
             device=get("DEVICE_TYPE", str, cls.device),
@@ -123,7 +125,8 @@ def train_model(model, train_loader, val_loader=None,
     criterion = criterion or CrossEntropyLoss()
     if optimizer is None:
         from .optim import Adam
-        optimizer = Adam(model.parameters(), lr=cfg.learning_rate)
+        optimizer = Adam(model.parameters(), lr=cfg.learning_rate,
+                         max_grad_norm=cfg.max_grad_norm)
     scheduler = scheduler or NoOpScheduler(optimizer)
     model.to(torch.device(cfg.device))
     history = []

@@ -33,6 +33,7 @@ from .functional import (
     group_norm,
     pointwise_loss,
     add_act,
+    grad_global_norm,
 )
 
 __all__ = [
@@ -57,4 +58,5 @@ __all__ = [
     "group_norm",
     "pointwise_loss",
     "add_act",
+    "grad_global_norm",
 ]

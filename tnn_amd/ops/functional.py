@@ -1097,3 +1097,31 @@ def sample_logits(logits: torch.Tensor, temperature: float = 1.0,
     first = torch.where(hit, idx, V).min(-1).values
     last_kept = torch.where(keep, idx, -1).max(-1).values
     return torch.where(first < V, first, last_kept)
+
+
+# ---------------------------------------------------------------------------
+# global gradient norm (the optimizers' clipping kernels, for logging)
+# ---------------------------------------------------------------------------
+
+def grad_global_norm(tensors) -> torch.Tensor:
+    """``sqrt(sum_i ||t_i||^2)`` over a list of tensors as a 0-dim fp32
+    tensor on their device, without a host sync.
+
+    On GPU this is the multi-tensor sum-of-squares kernel plus the
+    fixed-order finalize the optimizers use for ``max_grad_norm`` (fp32 and
+    bf16 read in place, anything else through a contiguous copy), so the
+    result is bitwise reproducible. On CPU it is the float64 torch form.
+    None entries are ignored.
+    """
+    tensors = [t.detach() for t in tensors if t is not None]
+    if _use_hip(*tensors):
+        from ..nn.optim import _GradNormWorkspace, _CLIP_NORM
+        dev = next(t.device for t in tensors if t.is_cuda)
+        ws = _GradNormWorkspace()
+        records = ws.loose_records(list(enumerate(tensors)), dev)
+        state = ws.run(_C.ext(), records, dev, 0.0, count_skips=False)
+        return state[_CLIP_NORM]
+    sumsq = torch.zeros((), dtype=torch.float64)
+    for t in tensors:
+        sumsq += t.double().pow(2).sum()
+    return sumsq.sqrt().float()

@@ -85,5 +85,8 @@ class DataParallelEngine:
     def train_step(self, loss: torch.Tensor, optimizer: Optimizer):
         loss.backward()
         self.finish_backward()
+        # gradient clipping (optimizer.max_grad_norm) needs no reduction of
+        # its own here: the bucketed all-reduce has been waited for, every
+        # rank holds identical gradients, the local norm IS the global one
         optimizer.step()
         optimizer.zero_grad()

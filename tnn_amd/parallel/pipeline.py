@@ -100,6 +100,12 @@ class PipelineEngine:
         opt_cfg = optimizer_config or {"type": "adamw", "lr": 1e-3}
         self.optimizer: Optimizer = optimizer_from_config(
             opt_cfg, self.stage.parameters())
+        if self.world > 1:
+            # stages own disjoint parameters: the clipping norm
+            # (max_grad_norm) must be the global one, so the local sum of
+            # squares is summed over the ranks before the coefficient and
+            # the skip decision are derived — the same on every stage
+            self.optimizer.norm_reduce = self.comm.allreduce_
         self.scheduler = (scheduler_from_config(scheduler_config, self.optimizer)
                           if scheduler_config else None)
         n_params = sum(p.numel() for p in self.stage.parameters())

@@ -49,9 +49,16 @@ class GraphedTrainStep:
     Adam bias correction reads the same counter instead of a baked-in
     host step — csrc/optim.hip, elementwise.hip, batchnorm.hip).
 
-    Constraints: fixed shapes, constant LR (schedulers would freeze), the
-    optimizer's python ``step_count`` stays at its capture value (the
-    device counter is the truth; checkpoint via ``sync_step_count()``).
+    The learning rate lives on the device too: the update kernels read
+    ``lr_dev``, and ``__call__`` refreshes it (one fill on the stream,
+    outside the graph, no sync) whenever ``optimizer.lr`` has changed, so a
+    scheduler stepped between calls takes effect. Gradient clipping
+    (``max_grad_norm``) needs nothing special: its two launches are
+    captured with the rest.
+
+    Constraints: fixed shapes, the optimizer's python ``step_count`` stays
+    at its capture value (the device counter is the truth; checkpoint via
+    ``sync_step_count()``).
     """
 
     def __init__(self, model, criterion, optimizer, example_x, example_y,
@@ -65,6 +72,10 @@ class GraphedTrainStep:
         self.step_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
         model.train()
         optimizer._step_dev = self.step_ctr
+        self.lr_dev = torch.full((1,), float(optimizer.lr),
+                                 dtype=torch.float32, device=dev)
+        self._lr_written = optimizer.lr
+        optimizer._lr_dev = self.lr_dev
         # pack all grads into per-dtype slabs (the reference GraphContext's
         # grad-slab idea): grad zeroing is then ONE fill per dtype instead
         # of a launch per parameter (torch._foreach_zero_ fell back to
@@ -112,6 +123,9 @@ class GraphedTrainStep:
             self.static_x.copy_(x)
         if y is not None:
             self.static_y.copy_(y)
+        if self.optimizer.lr != self._lr_written:
+            self.lr_dev.fill_(float(self.optimizer.lr))
+            self._lr_written = self.optimizer.lr
         self.graph.replay()
         return self.static_loss
 
