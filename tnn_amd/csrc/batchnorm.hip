@@ -5,8 +5,15 @@
 // NHWC: channels are the fast dim, so thread t of a block covers channel
 // (t % CPB) — global loads are perfectly coalesced across channels. All
 // statistics accumulate in fp32 regardless of io dtype (SURVEY §7 hard
-// part 5). Grid-level reduction: per-block partial sums combined with
-// fp32 atomics, then a tiny finalize kernel.
+// part 5). Grid-level reduction: per-block partial sums (slabs on the
+// vector path, fp32 atomics on the scalar one), then a tiny finalize kernel.
+//
+// The batch statistics are SHIFTED moments: every block subtracts the
+// per-channel shift K[c] = x[0, c] and accumulates sum(x-K), sum((x-K)^2);
+// finalize returns mean = K + s/n, var = ss/n - (s/n)^2. K is a sample of
+// the channel, so |mean - K| is a few std at most and the subtraction no
+// longer cancels when |mean| >> std (raw E[x^2] - mean^2 loses
+// (mean/std)^2 * 6e-8 of the variance in fp32).
 
 #include "common.h"
 #include "kernels.h"
@@ -18,7 +25,7 @@ template <typename T> struct alignas(16) BnPack {
   T e[16 / sizeof(T)];
 };
 
-// pass 1a: partial sum / sumsq per channel, atomics into f32 buffers
+// pass 1a: partial shifted sum / sumsq per channel, atomics into f32 buffers
 template <typename T>
 __global__ void k_bn_partial(const T* __restrict__ x, float* __restrict__ sum,
                              float* __restrict__ sumsq, int64_t rows,
@@ -30,9 +37,10 @@ __global__ void k_bn_partial(const T* __restrict__ x, float* __restrict__ sum,
   if (c >= cols || r_off >= rows_per_iter) return;
   const int64_t r0 = rows * blockIdx.y / gridDim.y;
   const int64_t r1 = rows * (blockIdx.y + 1) / gridDim.y;
+  const float k = VecIO<T>::to_f32(x[c]);  // shift: row 0 of the channel
   float s = 0.0f, ss = 0.0f;
   for (int64_t r = r0 + r_off; r < r1; r += rows_per_iter) {
-    float v = VecIO<T>::to_f32(x[r * cols + c]);
+    float v = VecIO<T>::to_f32(x[r * cols + c]) - k;
     s += v;
     ss += v * v;
   }
@@ -76,12 +84,16 @@ __global__ void k_bn_partial_vec(const T* __restrict__ x,
   if (g < groups && r_off < rows_per_iter) {
     const int64_t r0 = rows * blockIdx.y / gridDim.y;
     const int64_t r1 = rows * (blockIdx.y + 1) / gridDim.y;
+    const VecT vk = *(const VecT*)&x[(int64_t)g * V];  // shift: row 0
+    float k[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) k[j] = VecIO<T>::to_f32(vk.e[j]);
 #pragma unroll 4
     for (int64_t r = r0 + r_off; r < r1; r += rows_per_iter) {
       VecT v = *(const VecT*)&x[r * cols + (int64_t)g * V];
 #pragma unroll
       for (int j = 0; j < V; ++j) {
-        float f = VecIO<T>::to_f32(v.e[j]);
+        float f = VecIO<T>::to_f32(v.e[j]) - k[j];
         s[j] += f;
         ss[j] += f * f;
       }
@@ -184,14 +196,18 @@ __global__ void k_bn_bwd_reduce_vec(const T* __restrict__ x,
   }
 }
 
+// shift: row 0 of x when sum/sumsq are moments of x - shift[c]; null for
+// raw moments (the conv-epilogue sums)
+template <typename T>
 __global__ void k_bn_finalize(float* mean, float* invstd, const float* sum,
-                              const float* sumsq, float* rmean, float* rvar,
-                              float momentum, int64_t rows, int cols,
-                              float eps) {
+                              const float* sumsq, const T* shift, float* rmean,
+                              float* rvar, float momentum, int64_t rows,
+                              int cols, float eps) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
-  float m = sum[c] / rows;
-  float var = fmaxf(sumsq[c] / rows - m * m, 0.0f);
+  float d = sum[c] / rows;  // mean - shift
+  float var = fmaxf(sumsq[c] / rows - d * d, 0.0f);
+  float m = shift ? VecIO<T>::to_f32(shift[c]) + d : d;
   mean[c] = m;
   invstd[c] = rsqrtf(var + eps);
   if (rmean) {  // fused running-stat update (unbiased var, torch semantics)
@@ -494,9 +510,16 @@ void bn_stats_launch(DT dt, const void* x, float* mean, float* invstd,
       hipLaunchKernelGGL(k_bn_partial_vec<bf16>, g, dim3(256), 0, s,
                          (const bf16*)x, ws, nullptr, rows, cols);
     slab_fin_launch(ws, sums, (int)g.y, 2 * cols, s);
-    hipLaunchKernelGGL(k_bn_finalize, dim3((cols + 255) / 256), dim3(256), 0,
-                       s, mean, invstd, sums, sums + cols, rmean, rvar,
-                       momentum, rows, cols, eps);
+    if (dt == DT::F32)
+      hipLaunchKernelGGL(k_bn_finalize<float>, dim3((cols + 255) / 256),
+                         dim3(256), 0, s, mean, invstd, sums, sums + cols,
+                         (const float*)x, rmean, rvar, momentum, rows, cols,
+                         eps);
+    else
+      hipLaunchKernelGGL(k_bn_finalize<bf16>, dim3((cols + 255) / 256),
+                         dim3(256), 0, s, mean, invstd, sums, sums + cols,
+                         (const bf16*)x, rmean, rvar, momentum, rows, cols,
+                         eps);
     return;
   }
   // scalar fallback: mean/invstd double as zeroed atomic sum/sumsq
@@ -510,20 +533,27 @@ void bn_stats_launch(DT dt, const void* x, float* mean, float* invstd,
     hipLaunchKernelGGL(k_bn_partial<bf16>, bn_reduce_grid(rows, cols),
                        dim3(256), 0, s, (const bf16*)x, mean, invstd, rows,
                        cols);
-  hipLaunchKernelGGL(k_bn_finalize, dim3((cols + 255) / 256), dim3(256), 0, s,
-                     mean, invstd, mean, invstd, rmean, rvar, momentum, rows,
-                     cols, eps);
+  if (dt == DT::F32)
+    hipLaunchKernelGGL(k_bn_finalize<float>, dim3((cols + 255) / 256),
+                       dim3(256), 0, s, mean, invstd, mean, invstd,
+                       (const float*)x, rmean, rvar, momentum, rows, cols, eps);
+  else
+    hipLaunchKernelGGL(k_bn_finalize<bf16>, dim3((cols + 255) / 256),
+                       dim3(256), 0, s, mean, invstd, mean, invstd,
+                       (const bf16*)x, rmean, rvar, momentum, rows, cols, eps);
 }
 
 // finalize from precomputed sums (conv-epilogue fused stats): skips the
-// partial-reduce pass entirely
+// partial-reduce pass entirely. These are RAW moments (no shift), so this
+// path keeps the E[x^2] - mean^2 cancellation
 void bn_finalize_launch(const float* sum, const float* sumsq, float* mean,
                         float* invstd, float* rmean, float* rvar,
                         float momentum, int64_t rows, int cols, float eps,
                         hipStream_t s) {
-  hipLaunchKernelGGL(k_bn_finalize, dim3((cols + 255) / 256), dim3(256), 0, s,
-                     mean, invstd, sum, sumsq, rmean, rvar, momentum, rows,
-                     cols, eps);
+  hipLaunchKernelGGL(k_bn_finalize<float>, dim3((cols + 255) / 256),
+                     dim3(256), 0, s, mean, invstd, sum, sumsq,
+                     (const float*)nullptr, rmean, rvar, momentum, rows, cols,
+                     eps);
 }
 
 void bn_apply_launch(DT dt, const void* x, const float* mean,

@@ -584,24 +584,36 @@ __global__ void k_gemv_nn1(const T* __restrict__ x, const T* __restrict__ B,
     for (int k = threadIdx.x; k < K; k += 256)
       xs[k] = VecIO<T>::to_f32(x[k]);
     __syncthreads();
-    float sm = 0.0f, sq = 0.0f;
-    for (int k = threadIdx.x; k < K; k += 256) {
-      const float v = xs[k];
-      sm += v;
-      sq += v * v;
-    }
+    float sm = 0.0f;
+    for (int k = threadIdx.x; k < K; k += 256) sm += xs[k];
     sm = block_reduce_sum(sm, red[0]);
     __shared__ float bmean;
     if (threadIdx.x == 0) bmean = sm / (float)K;
     __syncthreads();
+    // centred variance from the LDS copy (matches ln_fwd; the raw
+    // E[x^2] - mean^2 form cancels in fp32 once |mean| >> std). The same
+    // pass sums x - mu: that residual dm is what fp32 rounding cut off the
+    // mean (up to ulp(mean)/2, which is 1e-5 of a std at mean/std = 256).
+    // x - mu is exact there, so (x - mu) - dm centres on the true mean;
+    // dm^2 <= 2^-48 mean^2 is left out of the variance.
+    const float mu = bmean;
+    float sq = 0.0f, sd = 0.0f;
+    for (int k = threadIdx.x; k < K; k += 256) {
+      const float d = xs[k] - mu;
+      sq += d * d;
+      sd += d;
+    }
     sq = block_reduce_sum(sq, red[0]);
-    __shared__ float binv;
-    if (threadIdx.x == 0)
-      binv = rsqrtf(fmaxf(sq / (float)K - bmean * bmean, 0.0f) + ln_eps);
+    sd = block_reduce_sum(sd, red[1]);
+    __shared__ float binv, bdm;
+    if (threadIdx.x == 0) {
+      binv = rsqrtf(sq / (float)K + ln_eps);
+      bdm = sd / (float)K;
+    }
     __syncthreads();
-    const float mu = bmean, is = binv;
+    const float is = binv, dm = bdm;
     for (int k = k_lo + (int)threadIdx.x; k < k_hi; k += 256)
-      xs[k] = (xs[k] - mu) * is * ln_g[k] + ln_b[k];
+      xs[k] = ((xs[k] - mu) - dm) * is * ln_g[k] + ln_b[k];
     __syncthreads();
   } else {
     for (int k = k_lo + (int)threadIdx.x; k < k_hi; k += 256)
@@ -702,6 +714,7 @@ void gemv_nn1_launch(DT dt, const void* x, const void* b, const void* bias,
 constexpr int SK_COLS = 128;  // columns per block
 constexpr int SK_KC = 512;    // k rows of x staged per LDS chunk
 constexpr int SK_U = 8;       // B loads in flight per lane
+constexpr int SK_LN_RC = 16;  // fused-LN row elements a lane keeps (K <= 1024)
 
 // One lane's two B elements of row `off / N`. c0 / c1 are already
 // clamped into the row by the caller, so the loads are unconditional: a
@@ -770,7 +783,7 @@ __global__ void k_gemm_skinny(const T* __restrict__ x, const T* __restrict__ B,
   constexpr int XS = SK_KC * MT;
   constexpr int RED = 3 * MT * SK_COLS;
   __shared__ alignas(16) float buf[XS > RED ? XS : RED];
-  __shared__ float mu_s[MT], is_s[MT];
+  __shared__ float mu_s[MT], dm_s[MT], is_s[MT];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int n0 = blockIdx.x * SK_COLS;
@@ -786,21 +799,52 @@ __global__ void k_gemm_skinny(const T* __restrict__ x, const T* __restrict__ B,
     // per-row LayerNorm statistics over the full row (recomputed by every
     // block, as in k_gemv_nn1): one wave per row
     for (int m = wave; m < M; m += 4) {
-      float sm = 0.0f, sq = 0.0f;
-      for (int k = lane; k < K; k += 64) {
-        const float v = VecIO<T>::to_f32(x[(int64_t)m * K + k]);
-        sm += v;
-        sq += v * v;
+      // two passes, centred on the mean. Rows of up to 64 * SK_LN_RC
+      // elements stay in registers between them (unconditional clamped
+      // loads, see sk_load); longer rows are read again from cache.
+      const T* xr = x + (int64_t)m * K;
+      const bool cached = K <= 64 * SK_LN_RC;
+      float xv[SK_LN_RC];
+      float sm = 0.0f;
+      if (cached) {
+#pragma unroll
+        for (int i = 0; i < SK_LN_RC; ++i) {
+          const int k = lane + 64 * i;
+          const float v = VecIO<T>::to_f32(xr[min(k, K - 1)]);
+          xv[i] = k < K ? v : 0.0f;
+          sm += xv[i];
+        }
+      } else {
+        for (int k = lane; k < K; k += 64) sm += VecIO<T>::to_f32(xr[k]);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off, 64);
+      // dm is the mean's fp32 rounding residual, as in k_gemv_nn1
+      const float mean = sm / (float)K;
+      float sq = 0.0f, sd = 0.0f;
+      if (cached) {
+#pragma unroll
+        for (int i = 0; i < SK_LN_RC; ++i) {
+          const float d = lane + 64 * i < K ? xv[i] - mean : 0.0f;
+          sq += d * d;
+          sd += d;
+        }
+      } else {
+        for (int k = lane; k < K; k += 64) {
+          const float d = VecIO<T>::to_f32(xr[k]) - mean;
+          sq += d * d;
+          sd += d;
+        }
       }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) {
-        sm += __shfl_xor(sm, off, 64);
         sq += __shfl_xor(sq, off, 64);
+        sd += __shfl_xor(sd, off, 64);
       }
       if (lane == 0) {
-        const float mean = sm / (float)K;
         mu_s[m] = mean;
-        is_s[m] = rsqrtf(fmaxf(sq / (float)K - mean * mean, 0.0f) + ln_eps);
+        dm_s[m] = sd / (float)K;
+        is_s[m] = rsqrtf(sq / (float)K + ln_eps);
       }
     }
     __syncthreads();
@@ -816,7 +860,8 @@ __global__ void k_gemm_skinny(const T* __restrict__ x, const T* __restrict__ B,
       if (m < M) {
         const int k = kc0 + kk;
         v = VecIO<T>::to_f32(x[(int64_t)m * K + k]);
-        if (ln_g) v = (v - mu_s[m]) * is_s[m] * ln_g[k] + ln_b[k];
+        if (ln_g)
+          v = ((v - mu_s[m]) - dm_s[m]) * is_s[m] * ln_g[k] + ln_b[k];
       }
       buf[kk * MT + m] = v;
     }
@@ -951,9 +996,15 @@ __global__ void k_gemm_skinny_mfma(const bf16* __restrict__ x,
   for (int i = threadIdx.x; i < XLD; i += 256) xs[16 * XLD + i] = f2bf(0.0f);
   if (ln_g) {
     for (int m = wave; m < M; m += 4) {
+      // shifted moments, one pass: the shift (the row's first element) is
+      // within a few std of the mean, so sq/K - d^2 keeps its digits where
+      // raw E[x^2] - mean^2 cancels. The two-pass form of k_gemm_skinny
+      // measured +1 us here (8%), and its extra accuracy would be lost in
+      // the bf16 staging below anyway.
+      const float k0 = bf2f(x[(int64_t)m * K]);
       float sm = 0.0f, sq = 0.0f;
       for (int k = lane; k < K; k += 64) {
-        const float v = bf2f(x[(int64_t)m * K + k]);
+        const float v = bf2f(x[(int64_t)m * K + k]) - k0;
         sm += v;
         sq += v * v;
       }
@@ -963,9 +1014,9 @@ __global__ void k_gemm_skinny_mfma(const bf16* __restrict__ x,
         sq += __shfl_xor(sq, off, 64);
       }
       if (lane == 0) {
-        const float mean = sm / (float)K;
-        mu_s[m] = mean;
-        is_s[m] = rsqrtf(fmaxf(sq / (float)K - mean * mean, 0.0f) + ln_eps);
+        const float d = sm / (float)K;  // mean - k0
+        mu_s[m] = k0 + d;
+        is_s[m] = rsqrtf(fmaxf(sq / (float)K - d * d, 0.0f) + ln_eps);
       }
     }
     __syncthreads();

@@ -11,7 +11,11 @@
 
 namespace tnn {
 
-// one 256-thread block per (n, g): sum/sumsq reduce -> mean, invstd
+// one 256-thread block per (n, g): shifted sum/sumsq reduce -> mean, invstd.
+// The shift k is the group's first element, a sample within a few std of
+// the mean, so ss/cnt - d^2 on the shifted sums does not cancel the way raw
+// E[x^2] - mean^2 does once |mean| >> std. (A second, centred pass measured
+// 1.65x the kernel time at CG = 4: the group's reads are strided.)
 template <typename T>
 __launch_bounds__(256)
 __global__ void k_gn_stats(const T* __restrict__ x, float* __restrict__ mean,
@@ -22,12 +26,13 @@ __global__ void k_gn_stats(const T* __restrict__ x, float* __restrict__ mean,
   const T* base = x + n * HW * C + g * CG;
   __shared__ float scratch[8];
 
+  const float k = VecIO<T>::to_f32(base[0]);
   float s = 0.0f, ss = 0.0f;
   const int64_t cnt = HW * CG;
   for (int64_t i = threadIdx.x; i < cnt; i += 256) {
     const int64_t p = i / CG;
     const int cc = (int)(i % CG);
-    const float v = VecIO<T>::to_f32(base[p * C + cc]);
+    const float v = VecIO<T>::to_f32(base[p * C + cc]) - k;
     s += v;
     ss += v * v;
   }
@@ -39,9 +44,9 @@ __global__ void k_gn_stats(const T* __restrict__ x, float* __restrict__ mean,
   __syncthreads();
   ss = block_reduce_sum(ss, scratch);
   if (threadIdx.x == 0) {
-    const float m = s / (float)cnt;
-    const float var = fmaxf(ss / (float)cnt - m * m, 0.0f);
-    mean[blockIdx.x] = m;
+    const float d = s / (float)cnt;  // mean - k
+    const float var = fmaxf(ss / (float)cnt - d * d, 0.0f);
+    mean[blockIdx.x] = k + d;
     invstd[blockIdx.x] = rsqrtf(var + eps);
   }
 }

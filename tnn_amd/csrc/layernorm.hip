@@ -33,9 +33,22 @@ DEV void block_reduce_sum2(float& a, float& b, float* scratch16) {
   }
 }
 
+// block-wide sum handed to EVERY thread of a 256-thread block: xor butterfly
+// inside the wave, one LDS slot per wave, one barrier, then each thread adds
+// the four wave sums in the same order (deterministic). Saves the second
+// barrier of reduce-to-thread-0 + broadcast. `scratch4` may not be rewritten
+// before the block's next barrier.
+DEV float block_allreduce_sum(float v, float* scratch4) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) scratch4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (scratch4[0] + scratch4[1]) + (scratch4[2] + scratch4[3]);
+}
+
 // vectorized one-block-per-row LN fwd: x held in registers across the
-// stats + write phases (the scalar form re-read global 3x and paid two
-// serial block reduces; measured 10.8us for a 6.3MB pass, ~4x roofline).
+// mean, centred-variance and write phases (the scalar form re-reads global
+// 3x; measured 10.8us for a 6.3MB pass, ~4x roofline).
 // PK = 16B packs per thread; requires cols % V == 0, cols <= PK*256*V.
 template <typename T, int PK>
 __launch_bounds__(256)
@@ -48,34 +61,39 @@ __global__ void k_ln_fwd_vec(const T* __restrict__ x, const float* gamma,
   const int64_t row = blockIdx.x;
   const T* xr = x + row * cols;
   const int npk = cols / V;
-  __shared__ float scratch[16];
-  __shared__ float s_m, s_is;
+  __shared__ float scratch[8];
 
   P v[PK];
-  float s = 0.0f, ss = 0.0f;
+  float s = 0.0f;
 #pragma unroll
   for (int k = 0; k < PK; ++k) {
     const int pk = threadIdx.x + k * 256;
     if (pk < npk) {
       v[k] = ((const P*)xr)[pk];
 #pragma unroll
+      for (int j = 0; j < V; ++j) s += VecIO<T>::to_f32(v[k].e[j]);
+    }
+  }
+  // centred second moment from the registers: E[x^2] - mean^2 cancels to
+  // nothing in fp32 once |mean| >> std
+  const float m = block_allreduce_sum(s, scratch) / cols;
+  float ss = 0.0f;
+#pragma unroll
+  for (int k = 0; k < PK; ++k) {
+    const int pk = threadIdx.x + k * 256;
+    if (pk < npk) {
+#pragma unroll
       for (int j = 0; j < V; ++j) {
-        const float f = VecIO<T>::to_f32(v[k].e[j]);
-        s += f;
-        ss += f * f;
+        const float d = VecIO<T>::to_f32(v[k].e[j]) - m;
+        ss += d * d;
       }
     }
   }
-  block_reduce_sum2(s, ss, scratch);
+  const float is = rsqrtf(block_allreduce_sum(ss, scratch + 4) / cols + eps);
   if (threadIdx.x == 0) {
-    const float m = s / cols;
-    s_m = m;
-    s_is = rsqrtf(fmaxf(ss / cols - m * m, 0.0f) + eps);
     mean[row] = m;
-    invstd[row] = s_is;
+    invstd[row] = is;
   }
-  __syncthreads();
-  const float m = s_m, is = s_is;
   T* yr = y + row * cols;
 #pragma unroll
   for (int k = 0; k < PK; ++k) {
