@@ -2,8 +2,9 @@
 
 Small shapes that reach every way the loop can go: chunk counts 1 / 2 / odd /
 even, chunks that span several (kh,kw) slices, the ragged last chunk, M and
-Cout tails, several tiles, stride 2 (dgrad parity route), 1x1 stride 2, and
-the K = 4608 deep-layer shape.
+Cout tails, several tiles, stride 2 (dgrad parity route), 1x1 stride 2, the
+K = 4608 deep-layer shape, and stride 4 (the dgrad kernels that test the
+stride divisibility at run time).
 
 Every case is checked twice: against torch in fp32 on the same bf16 inputs,
 and bitwise against the same build routed to the single-buffer kernels with
@@ -49,6 +50,7 @@ CASES = [
     (2, 8, 8, 64, 128, 3, 2, 1),     # fwd stride 2; dgrad parity route
     (2, 8, 8, 64, 128, 1, 2, 0),     # 1x1 stride 2
     (1, 4, 4, 512, 512, 3, 1, 1),    # K = 4608
+    (1, 16, 16, 64, 64, 3, 4, 1),    # stride 4: dgrad generic-stride route
 ]
 IDS = ["x".join(map(str, c)) for c in CASES]
 

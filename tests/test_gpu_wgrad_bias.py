@@ -67,15 +67,17 @@ def _ref(x, dy, K, S, P):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(name):
+def _case(name, dtype=torch.bfloat16):
     """Inputs, one float64 reference and the kernel's fp32 result per case,
-    computed once and shared (read-only) by the tests below."""
+    computed once and shared (read-only) by the tests below. fp32 inputs
+    hold the same bf16-rounded values, so their products stay exact in fp32
+    and the bound above holds as written."""
     N, H, W, Ci, Co, K, S, P = CASES[name]
     g = torch.Generator().manual_seed(sum(map(ord, name)))
     OH = (H + 2 * P - K) // S + 1
     OW = (W + 2 * P - K) // S + 1
-    x = torch.randn(N, H, W, Ci, generator=g).bfloat16().to(DEV)
-    dy = torch.randn(N, OH, OW, Co, generator=g).bfloat16().to(DEV)
+    x = torch.randn(N, H, W, Ci, generator=g).bfloat16().to(dtype).to(DEV)
+    dy = torch.randn(N, OH, OW, Co, generator=g).bfloat16().to(dtype).to(DEV)
     ref = _ref(x, dy, K, S, P)
     dw, db = ext.conv2d_wgrad_bias(x, dy, K, K, S, S, P, P, False)
     return x, dy, ref, dw, db
@@ -99,6 +101,17 @@ def _check(dw, db, ref, extra_rel=0.0):
 def test_wgrad_bias_fp32_out(name):
     x, dy, ref, dw, db = _case(name)
     N, H, W, Ci, Co, K, S, P = CASES[name]
+    assert dw.shape == (K, K, Ci, Co) and dw.dtype == torch.float32
+    assert db.shape == (Co,) and db.dtype == torch.float32
+    _check(dw, db, ref)
+
+
+@pytest.mark.parametrize("name", ["tails", "exact", "stride2", "nonpow2"])
+def test_wgrad_bias_fp32_out_fp32_in(name):
+    """the bias row of the fp32 kernels (vector route and generic fallback)"""
+    x, dy, ref, dw, db = _case(name, torch.float32)
+    N, H, W, Ci, Co, K, S, P = CASES[name]
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32
     assert dw.shape == (K, K, Ci, Co) and dw.dtype == torch.float32
     assert db.shape == (Co,) and db.dtype == torch.float32
     _check(dw, db, ref)

@@ -388,12 +388,14 @@ at::Tensor mfma_selftest_f32(const at::Tensor& a, const at::Tensor& b) {
 }
 
 // ---- conv2d ----------------------------------------------------------------
-static ConvShape conv_shape(const at::Tensor& x_like, int Cin, int Cout, int KH,
-                            int KW, int SH, int SW, int PH, int PW) {
+// shape of the conv whose input is [N, H, W, Cin] and output [N, OH, OW, Cout]
+static ConvShape conv_shape_out(int N, int H, int W, int Cin, int Cout, int KH,
+                                int KW, int SH, int SW, int PH, int PW, int OH,
+                                int OW) {
   ConvShape cs;
-  cs.N = x_like.size(0);
-  cs.H = x_like.size(1);
-  cs.W = x_like.size(2);
+  cs.N = N;
+  cs.H = H;
+  cs.W = W;
   cs.Cin = Cin;
   cs.Cout = Cout;
   cs.KH = KH;
@@ -402,15 +404,28 @@ static ConvShape conv_shape(const at::Tensor& x_like, int Cin, int Cout, int KH,
   cs.SW = SW;
   cs.PH = PH;
   cs.PW = PW;
-  cs.OH = (cs.H + 2 * PH - KH) / SH + 1;
-  cs.OW = (cs.W + 2 * PW - KW) / SW + 1;
+  cs.OH = OH;
+  cs.OW = OW;
   cs.init_fdiv();
   return cs;
 }
 
-at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
-                      const c10::optional<at::Tensor>& bias, int64_t sh,
-                      int64_t sw, int64_t ph, int64_t pw, bool relu) {
+static ConvShape conv_shape(const at::Tensor& x, int Cin, int Cout, int KH,
+                            int KW, int SH, int SW, int PH, int PW) {
+  int H = x.size(1), W = x.size(2);
+  return conv_shape_out(x.size(0), H, W, Cin, Cout, KH, KW, SH, SW, PH, PW,
+                        (H + 2 * PH - KH) / SH + 1, (W + 2 * PW - KW) / SW + 1);
+}
+
+// Returns {y, stats}. want_stats asks for the fused per-channel sum/sumsq
+// [2, Cout] of y (linear act); it comes from the DMA-staged kernels only
+// (k_conv_fwd_db / k_conv_fwd_sb), so where those are not eligible (non-pow2
+// dims, unaligned x, fp32 with K > 2304, TNN_FWD_DB=0) stats is EMPTY and y
+// is computed by the plain route all the same.
+static std::vector<at::Tensor> conv2d_fwd_impl(
+    const at::Tensor& x, const at::Tensor& w,
+    const c10::optional<at::Tensor>& bias, int64_t sh, int64_t sw, int64_t ph,
+    int64_t pw, bool relu, bool want_stats) {
   CHECK_IN(x);
   CHECK_IN(w);
   TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && x.size(3) == w.size(2),
@@ -422,59 +437,42 @@ at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
   auto cs = conv_shape(x, w.size(2), w.size(3), w.size(0), w.size(1), sh, sw,
                        ph, pw);
   auto y = at::empty({cs.N, cs.OH, cs.OW, cs.Cout}, x.options());
-  const void* bp = bias.has_value() ? bias->data_ptr() : nullptr;
-  at::Tensor wt2;
-  const void* wt2p = nullptr;
-  if (conv2d_fwd_wants_db(dt_of(x), x.data_ptr(), cs)) {
+  at::Tensor wt2, stats;
+  const bool db = conv2d_fwd_wants_db(dt_of(x), x.data_ptr(), cs);
+  if (db) {
     wt2 = at::empty({(int64_t)cs.Cout, (int64_t)cs.KH * cs.KW * cs.Cin},
                     w.options());
     transpose_w_fwd_launch(dt_of(x), w.data_ptr(), wt2.data_ptr(),
                            cs.KH * cs.KW, cs.Cin, cs.Cout, cur_stream());
-    wt2p = wt2.data_ptr();
   }
-  conv2d_fwd_launch(dt_of(x), x.data_ptr(), w.data_ptr(), wt2p, bp,
-                    y.data_ptr(), zero_page(x), nullptr, cs, relu,
-                    cur_stream());
-  return y;
+  if (want_stats)
+    stats = db ? at::zeros({2, (int64_t)cs.Cout},
+                           x.options().dtype(at::kFloat))
+               : at::empty({0}, x.options().dtype(at::kFloat));
+  conv2d_fwd_launch(dt_of(x), x.data_ptr(), w.data_ptr(),
+                    db ? wt2.data_ptr() : nullptr,
+                    bias.has_value() ? bias->data_ptr() : nullptr,
+                    y.data_ptr(), zero_page(x),
+                    db && want_stats ? stats.data_ptr<float>() : nullptr, cs,
+                    relu, cur_stream());
+  return {y, stats};
+}
+
+at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
+                      const c10::optional<at::Tensor>& bias, int64_t sh,
+                      int64_t sw, int64_t ph, int64_t pw, bool relu) {
+  return conv2d_fwd_impl(x, w, bias, sh, sw, ph, pw, relu, false)[0];
 }
 
 // conv fwd + fused per-channel sum/sumsq for a following train-mode BN
-// (linear act). Returns {y, stats[2, Cout]}; stats is EMPTY when no
-// DMA-staged kernel (k_conv_fwd_db / k_conv_fwd_sb, the ones carrying the
-// stats epilogue) is eligible -- callers fall back to the separate BN stats
-// pass.
+// (linear act). Returns {y, stats[2, Cout]}; callers fall back to the
+// separate BN stats pass when stats comes back empty.
 std::vector<at::Tensor> conv2d_fwd_stats(const at::Tensor& x,
                                          const at::Tensor& w,
                                          const c10::optional<at::Tensor>& bias,
                                          int64_t sh, int64_t sw, int64_t ph,
                                          int64_t pw) {
-  CHECK_IN(x);
-  CHECK_IN(w);
-  auto cs = conv_shape(x, w.size(2), w.size(3), w.size(0), w.size(1), sh, sw,
-                       ph, pw);
-  auto y = at::empty({cs.N, cs.OH, cs.OW, cs.Cout}, x.options());
-  const void* bp = bias.has_value() ? bias->data_ptr() : nullptr;
-  if (!conv2d_fwd_wants_db(dt_of(x), x.data_ptr(), cs)) {
-    // stats fusion needs a DMA-staged kernel; ineligible shapes (non-pow2
-    // dims, unaligned x, fp32 with K > 2304, TNN_FWD_DB=0) still must
-    // COMPUTE y via the plain path. (Round-1 latent bug: this
-    // early return handed back uninitialized y — garbage activations for
-    // every 512-channel conv under BN training.)
-    conv2d_fwd_launch(dt_of(x), x.data_ptr(), w.data_ptr(), nullptr, bp,
-                      y.data_ptr(), zero_page(x), nullptr, cs,
-                      /*relu=*/false, cur_stream());
-    return {y, at::empty({0}, x.options().dtype(at::kFloat))};
-  }
-  auto wt2 = at::empty({(int64_t)cs.Cout, (int64_t)cs.KH * cs.KW * cs.Cin},
-                       w.options());
-  transpose_w_fwd_launch(dt_of(x), w.data_ptr(), wt2.data_ptr(),
-                         cs.KH * cs.KW, cs.Cin, cs.Cout, cur_stream());
-  auto stats = at::zeros({2, (int64_t)cs.Cout},
-                         x.options().dtype(at::kFloat));
-  conv2d_fwd_launch(dt_of(x), x.data_ptr(), w.data_ptr(), wt2.data_ptr(), bp,
-                    y.data_ptr(), zero_page(x), stats.data_ptr<float>(), cs,
-                    /*relu=*/false, cur_stream());
-  return {y, stats};
+  return conv2d_fwd_impl(x, w, bias, sh, sw, ph, pw, /*relu=*/false, true);
 }
 
 at::Tensor conv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H,
@@ -483,21 +481,8 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H,
   CHECK_IN(dy);
   CHECK_IN(w);
   int KH = w.size(0), KW = w.size(1), Cin = w.size(2), Cout = w.size(3);
-  ConvShape cs;
-  cs.N = dy.size(0);
-  cs.H = H;
-  cs.W = W;
-  cs.Cin = Cin;
-  cs.Cout = Cout;
-  cs.KH = KH;
-  cs.KW = KW;
-  cs.SH = sh;
-  cs.SW = sw;
-  cs.PH = ph;
-  cs.PW = pw;
-  cs.OH = dy.size(1);
-  cs.OW = dy.size(2);
-  cs.init_fdiv();
+  auto cs = conv_shape_out(dy.size(0), H, W, Cin, Cout, KH, KW, sh, sw, ph, pw,
+                           dy.size(1), dy.size(2));
   auto dx = at::empty({cs.N, H, W, Cin}, dy.options());
   if (conv2d_dgrad_wants_db(dt_of(dy), dy.data_ptr(), cs)) {
     // double-buffered path: weight as [Cin][(kh,kw,co)] k-contiguous rows

@@ -52,6 +52,287 @@ DEV void kdecode(int kidx, const ConvShape& cs, int& kh, int& kw) {
 }
 
 // ---------------------------------------------------------------------------
+// pieces shared by the kernel bodies below
+// ---------------------------------------------------------------------------
+
+// this block's (tm, tn) tile: grouped tile order once the gathered activation
+// stream (im2col elements) exceeds the 256 MiB L3 across its n-tile re-reads
+// (see tile_gemm.h), dispatch order below that
+DEV void conv_tile_order(const ConvShape& cs, int& tm, int& tn) {
+  if ((int64_t)cs.N * cs.OH * cs.OW * (cs.KH * cs.KW * cs.Cin) >
+      (int64_t)32 * 1024 * 1024)
+    tile::tile_remap_xcd<4>(tm, tn);
+  else {
+    tm = blockIdx.x;
+    tn = blockIdx.y;
+  }
+}
+
+// ---- forward gather: im2col element (gm, gk) of x --------------------------
+// row gm = (n, oh, ow), held as the image and the input pixel of tap (0, 0)
+struct FwdRow { int n, ih0, iw0; };
+template <bool POW2>
+DEV FwdRow fwd_row(const ConvShape& cs, int gm) {
+  int n = idiv<POW2>(gm, cs.d_ohow);
+  int rem = gm - n * (cs.OH * cs.OW);
+  int oh = idiv<POW2>(rem, cs.d_ow), ow = rem - oh * cs.OW;
+  return {n, oh * cs.SH - cs.PH, ow * cs.SW - cs.PW};
+}
+// address of x at k index gk = (kh, kw, ci), or oob (null, the zero page)
+// when the tap falls into the padding
+template <bool POW2, typename T>
+DEV const T* fwd_src(const T* __restrict__ X, const ConvShape& cs,
+                     const FwdRow& r, int gk, const T* oob) {
+  int ci = imod<POW2>(gk, cs.d_cin);
+  int kidx = idiv<POW2>(gk, cs.d_cin);
+  int kh, kw;
+  kdecode(kidx, cs, kh, kw);
+  int ih = r.ih0 + kh;
+  int iw = r.iw0 + kw;
+  if (ih < 0 || ih >= cs.H || iw < 0 || iw >= cs.W) return oob;
+  return &X[(((int64_t)r.n * cs.H + ih) * cs.W + iw) * cs.Cin + ci];
+}
+// 16 bytes of row r at k indices [gk, gk + V), zero in the padding and at or
+// past K: one vector load when the run lies in one (kh,kw) slice, else
+// element-wise
+template <bool POW2, typename T>
+DEV Pack16<T> fwd_gather16(const T* __restrict__ X, const ConvShape& cs,
+                           const FwdRow& r, int gk, int K) {
+  constexpr int V = 16 / sizeof(T);
+  Pack16<T> v = {};
+  const T* const none = nullptr;
+  if (imod<POW2>(gk, cs.d_cin) + V <= cs.Cin && gk + V <= K &&
+      (cs.Cin % V) == 0 && aligned16(X)) {
+    if (const T* p = fwd_src<POW2>(X, cs, r, gk, none))
+      v = *(const Pack16<T>*)p;
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      if (gk + j >= K) continue;
+      if (const T* p = fwd_src<POW2>(X, cs, r, gk + j, none)) v.e[j] = *p;
+    }
+  }
+  return v;
+}
+
+// ---- dgrad gather: dy element behind dx pixel (n, ih, iw) and tap (kh, kw) --
+// S2: stride-2 parity decomposition. blockIdx.z selects the (ih%2, iw%2) class
+// so every (kh,kw) visited satisfies the stride divisibility test by
+// construction -- the generic kernel at stride 2 burns 3/4 of its MFMAs
+// multiplying gathered zeros. A class is an M/4-row problem over the
+// compacted taps (khi, kwi) -> (start_h + 2 khi, start_w + 2 kwi); the
+// launcher rewrites cs.d_hw/d_w to the per-class (Hc*Wc, Wc) divisors.
+// Without S2 the one "class" is the whole problem.
+struct DgradTap { int khi, kwi, kh, kw, widx; };  // widx: tap index kh*KW+kw
+template <bool S2>
+struct DgradClass {
+  int cls_a, cls_b, start_h, start_w, nkh, nkw, Hc, Wc, M, K;
+  DEV explicit DgradClass(const ConvShape& cs) {
+    cls_a = S2 ? ((int)blockIdx.z >> 1) : 0;
+    cls_b = S2 ? ((int)blockIdx.z & 1) : 0;
+    start_h = S2 ? ((cls_a + cs.PH) & 1) : 0;
+    start_w = S2 ? ((cls_b + cs.PW) & 1) : 0;
+    nkh = S2 ? ((cs.KH - start_h + 1) >> 1) : cs.KH;
+    nkw = S2 ? ((cs.KW - start_w + 1) >> 1) : cs.KW;
+    Hc = S2 ? (cs.H >> 1) : cs.H;
+    Wc = S2 ? (cs.W >> 1) : cs.W;
+    M = cs.N * Hc * Wc;
+    K = nkh * nkw * cs.Cout;
+  }
+  // kidx = k index / Cout of this class -> its tap
+  DEV DgradTap tap(const ConvShape& cs, int kidx) const {
+    DgradTap t;
+    if constexpr (S2) {
+      t.kwi = kidx & (nkw - 1);              // nkw is 1 or 2
+      t.khi = nkw == 2 ? (kidx >> 1) : kidx;
+      t.kh = start_h + 2 * t.khi;
+      t.kw = start_w + 2 * t.kwi;
+      t.widx = t.kh * cs.KW + start_w + 2 * t.kwi;
+    } else {
+      kdecode(kidx, cs, t.kh, t.kw);
+      t.khi = t.kh;
+      t.kwi = t.kw;
+      t.widx = kidx;
+    }
+    return t;
+  }
+  // class row -> (n, ih, iw) of dx
+  template <bool POW2>
+  DEV void coords(const ConvShape& cs, int row, int& n, int& ih, int& iw) const {
+    n = idiv<POW2>(row, cs.d_hw);
+    int rem = row - n * (Hc * Wc);
+    ih = idiv<POW2>(rem, cs.d_w);
+    iw = rem - ih * Wc;
+    if constexpr (S2) {
+      ih = 2 * ih + cls_a;
+      iw = 2 * iw + cls_b;
+    }
+  }
+  // class row -> pixel index of dx
+  template <bool POW2>
+  DEV int64_t pixel(const ConvShape& cs, int row) const {
+    if constexpr (!S2) return row;
+    int n, ih, iw;
+    coords<POW2>(cs, row, n, ih, iw);
+    return ((int64_t)n * cs.H + ih) * cs.W + iw;
+  }
+};
+// address of dy at (n, oh, ow, co), the output pixel that feeds dx pixel
+// (ih, iw) through tap (kh, kw), or oob (null, the zero page) when there is
+// none. S2: th, tw are even by construction; S1: oh == th; otherwise the
+// stride is tested at run time.
+template <bool S2, bool S1, typename T>
+DEV const T* dgrad_src(const T* __restrict__ DY, const ConvShape& cs, int n,
+                       int ih, int iw, int kh, int kw, int co, const T* oob) {
+  int th = ih + cs.PH - kh, tw = iw + cs.PW - kw;
+  int oh, ow;
+  if constexpr (S2) {
+    if (th < 0 || tw < 0) return oob;
+    oh = th >> 1, ow = tw >> 1;
+    if (oh >= cs.OH || ow >= cs.OW) return oob;
+  } else if constexpr (S1) {
+    if (th < 0 || tw < 0 || th >= cs.OH || tw >= cs.OW) return oob;
+    oh = th, ow = tw;
+  } else {
+    if (th < 0 || tw < 0 || th % cs.SH || tw % cs.SW) return oob;
+    oh = th / cs.SH, ow = tw / cs.SW;
+    if (oh >= cs.OH || ow >= cs.OW) return oob;
+  }
+  return &DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) * cs.Cout + co];
+}
+
+// ---- register-staged operand images ----------------------------------------
+// A: the [BM][BK] image of rows m0.. and k indices k0.., gathered 16 bytes at
+// a time by gather(gm, gk); rows >= M and k >= K are zero
+template <typename T, typename GatherFn>
+DEV void stage_a_gathered(T* As, int m0, int k0, int M, int K,
+                          GatherFn&& gather) {
+  constexpr int V = 16 / sizeof(T);
+#pragma unroll
+  for (int c = threadIdx.x; c < BM * (BK / V); c += THREADS) {
+    int row = c / (BK / V);
+    int kk = (c % (BK / V)) * V;
+    int gm = m0 + row, gk = k0 + kk;
+    Pack16<T> v = {};
+    if (gm < M && gk < K) v = gather(gm, gk);
+    *(Pack16<T>*)&As[lds_off<T>(row, kk)] = v;
+  }
+}
+// B: rows k0.. of a row-major matrix (rowptr(gk) -> its row, ncols wide),
+// columns n0.., scatter-transposed into the image Bs[n][k]; rows >= K and
+// columns >= ncols are zero
+template <typename T, typename RowFn>
+DEV void stage_b_transposed(T* Bs, RowFn&& rowptr, int ncols, int n0, int k0,
+                            int K) {
+  constexpr int V = 16 / sizeof(T);
+#pragma unroll
+  for (int c = threadIdx.x; c < BK * (BN / V); c += THREADS) {
+    int kk = c / (BN / V);
+    int nn = (c % (BN / V)) * V;
+    int gk = k0 + kk;
+    Pack16<T> v = {};
+    if (gk < K) v = load16_guarded(rowptr(gk), n0 + nn, ncols);
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      Bs[lds_off<T>(nn + j, kk)] = v.e[j];
+  }
+}
+
+// ---- epilogues --------------------------------------------------------------
+// Their pointer parameters carry no __restrict__ of their own: the kernels'
+// qualifiers hold after inlining, and repeating them here changed the
+// instruction selection of the DMA-staged kernels' epilogues.
+
+// fwd: y = act(acc + bias), cast store
+template <typename T>
+DEV void conv_fwd_store(const WaveCoord& wc, f32x4 acc[FM][FN], const T* bias,
+                        T* Y, const ConvShape& cs, int act_kind, int m0,
+                        int n0, int M) {
+  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
+    if (row < M && col < cs.Cout) {
+      if (bias) v += VecIO<T>::to_f32(bias[col]);
+      if (act_kind != ACT_LINEAR) v = act_apply(v, act_kind);
+      Y[(int64_t)row * cs.Cout + col] = VecIO<T>::from_f32(v);
+    }
+  });
+}
+
+// fwd fused statistics: per-channel sum/sumsq of the tile straight from the
+// accumulators (post-bias, linear act only): saves the BN stats pass's full
+// read of y. C/D fragment col = lane&15; lanes {l, l+16, l+32, l+48} share
+// a column -> two shfl_xor folds, then one atomic per (block, col).
+template <typename T>
+DEV void conv_fwd_stats(const WaveCoord& wc, f32x4 acc[FM][FN],
+                        const T* bias_p, float* stats, const ConvShape& cs,
+                        int m0, int n0, int M) {
+  float* ssum = stats;
+  float* ssumsq = stats + cs.Cout;
+  const int cr = (wc.lane >> 4) * 4;
+  const int cc = wc.lane & 15;
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    int col = n0 + wc.wcol0 + fn * 16 + cc;
+    float bias = 0.0f;
+    if (col < cs.Cout) {
+      if (bias_p) bias = VecIO<T>::to_f32(bias_p[col]);
+    }
+    float s = 0.0f, ss = 0.0f;
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int row = m0 + wc.wrow0 + fm * 16 + cr + j;
+        if (row < M && col < cs.Cout) {
+          float v = acc[fm][fn][j] + bias;
+          s += v;
+          ss += v * v;
+        }
+      }
+    s += __shfl_xor(s, 16, 64);
+    ss += __shfl_xor(ss, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    ss += __shfl_xor(ss, 32, 64);
+    if (wc.lane < 16 && col < cs.Cout) {
+      atomicAdd(&ssum[col], s);
+      atomicAdd(&ssumsq[col], ss);
+    }
+  }
+}
+
+// dgrad: cast store of a class's rows to their dx pixels
+template <bool POW2, typename T, bool S2>
+DEV void dgrad_store(const WaveCoord& wc, f32x4 acc[FM][FN], T* DX,
+                     const ConvShape& cs, const DgradClass<S2>& dc, int m0,
+                     int n0) {
+  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
+    if (row < dc.M && col < cs.Cin)
+      DX[dc.template pixel<POW2>(cs, row) * cs.Cin + col] =
+          VecIO<T>::from_f32(v);
+  });
+}
+
+// wgrad: block z's tile into slab z of the [z][Kout + bias_row][Cout] fp32
+// workspace; returns the slab
+DEV float* wgrad_slab_store(const WaveCoord& wc, f32x4 acc[FM][FN],
+                            float* DW, const ConvShape& cs, int Kout,
+                            int bias_row, int r0, int n0) {
+  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
+  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
+    if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
+  });
+  return out;
+}
+// bias gradient of the register-staged kernels: the per-thread dy column
+// partials bsum of a tile-row-0 block, folded into row Kout of its slab
+DEV void wgrad_colsum_store(float* out, const ConvShape& cs, int Kout, int n0,
+                            float bsum) {
+  bsum = colsum_tile_finish(bsum);
+  int col = n0 + (threadIdx.x >> 2);
+  if ((threadIdx.x & 3) == 0 && col < cs.Cout)
+    out[(int64_t)Kout * cs.Cout + col] = bsum;
+}
+
+// ---------------------------------------------------------------------------
 // double-buffered k-loop shared by k_conv_fwd_db and k_conv_dgrad_db, fp32
 // and bf16 (all-pow2 shapes, gathered channel count C = 1 << lgC a multiple
 // of the 16-byte vector width).
@@ -204,25 +485,16 @@ DEV void conv_db_kloop(T* As0, T* As1, T* Bs0, T* Bs1,
 // next chunk's DMAs overlap the current chunk's MFMAs. Counted
 // s_waitcnt vmcnt + raw s_barrier per the CDNA4 glds idiom -- a
 // __syncthreads() here would drain the in-flight next-chunk DMAs.
-template <typename T, bool POW2, bool STATS, bool DB>
+template <typename T, bool STATS, bool DB>
 DEV void conv_fwd_glds_tile(const T* __restrict__ X,
                             const T* __restrict__ WT2,
-                            const float* __restrict__ bias_f32,
-                            const T* __restrict__ bias_t, T* __restrict__ Y,
+                            const T* __restrict__ bias, T* __restrict__ Y,
                             const T* __restrict__ zero16, const ConvShape& cs,
                             int act_kind, float* __restrict__ stats) {
   const int M = cs.N * cs.OH * cs.OW;
   const int K = cs.KH * cs.KW * cs.Cin;
   int tm_, tn_;
-  // grouped tile ordering when the gathered activation stream exceeds
-  // the 256 MiB L3 across its Cout/BN re-reads (see tile_gemm.h)
-  if ((int64_t)cs.N * cs.OH * cs.OW * (cs.KH * cs.KW * cs.Cin) >
-      (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tm_, tn_);
-  else {
-    tm_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  conv_tile_order(cs, tm_, tn_);
   const int m0 = tm_ * BM;
   const int n0 = tn_ * BN;
   const WaveCoord wc;
@@ -260,66 +532,19 @@ DEV void conv_fwd_glds_tile(const T* __restrict__ X,
                          zero16, row, tap, at);
   }
 
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < cs.Cout) {
-      if (bias_f32) v += bias_f32[col];
-      if (bias_t) v += VecIO<T>::to_f32(bias_t[col]);
-      if (act_kind != ACT_LINEAR) v = act_apply(v, act_kind);
-      Y[(int64_t)row * cs.Cout + col] = VecIO<T>::from_f32(v);
-    }
-  });
-
-  if constexpr (STATS) {
-    // per-channel sum/sumsq of the tile straight from the accumulators
-    // (post-bias, linear act only): saves the BN stats pass's full read
-    // of y. C/D fragment col = lane&15; lanes {l, l+16, l+32, l+48} share
-    // a column -> two shfl_xor folds, then one atomic per (block, col).
-    float* ssum = stats;
-    float* ssumsq = stats + cs.Cout;
-    const int cr = (wc.lane >> 4) * 4;
-    const int cc = wc.lane & 15;
-#pragma unroll
-    for (int fn = 0; fn < FN; ++fn) {
-      int col = n0 + wc.wcol0 + fn * 16 + cc;
-      float bias = 0.0f;
-      if (col < cs.Cout) {
-        if (bias_f32) bias = bias_f32[col];
-        if (bias_t) bias = VecIO<T>::to_f32(bias_t[col]);
-      }
-      float s = 0.0f, ss = 0.0f;
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int row = m0 + wc.wrow0 + fm * 16 + cr + j;
-          if (row < M && col < cs.Cout) {
-            float v = acc[fm][fn][j] + bias;
-            s += v;
-            ss += v * v;
-          }
-        }
-      s += __shfl_xor(s, 16, 64);
-      ss += __shfl_xor(ss, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      ss += __shfl_xor(ss, 32, 64);
-      if (wc.lane < 16 && col < cs.Cout) {
-        atomicAdd(&ssum[col], s);
-        atomicAdd(&ssumsq[col], ss);
-      }
-    }
-  }
+  conv_fwd_store(wc, acc, bias, Y, cs, act_kind, m0, n0, M);
+  if constexpr (STATS) conv_fwd_stats(wc, acc, bias, stats, cs, m0, n0, M);
 }
 
-template <typename T, bool POW2, bool STATS = false>
+template <typename T, bool STATS = false>
 __launch_bounds__(THREADS)
 __global__ void k_conv_fwd_db(const T* __restrict__ X,
                               const T* __restrict__ WT2,
-                              const float* __restrict__ bias_f32,
-                              const T* __restrict__ bias_t, T* __restrict__ Y,
+                              const T* __restrict__ bias, T* __restrict__ Y,
                               const T* __restrict__ zero16, ConvShape cs,
                               int act_kind, float* __restrict__ stats) {
-  conv_fwd_glds_tile<T, POW2, STATS, true>(X, WT2, bias_f32, bias_t, Y, zero16,
-                                           cs, act_kind, stats);
+  conv_fwd_glds_tile<T, STATS, true>(X, WT2, bias, Y, zero16, cs, act_kind,
+                                     stats);
 }
 
 // the same tile on one LDS buffer pair for the long k-loops past the double
@@ -329,43 +554,35 @@ template <bool STATS>
 __launch_bounds__(THREADS)
 __global__ void k_conv_fwd_sb(const bf16* __restrict__ X,
                               const bf16* __restrict__ WT2,
-                              const bf16* __restrict__ bias_t,
+                              const bf16* __restrict__ bias,
                               bf16* __restrict__ Y,
                               const bf16* __restrict__ zero16, ConvShape cs,
                               int act_kind, float* __restrict__ stats) {
-  conv_fwd_glds_tile<bf16, true, STATS, false>(X, WT2, nullptr, bias_t, Y,
-                                               zero16, cs, act_kind, stats);
+  conv_fwd_glds_tile<bf16, STATS, false>(X, WT2, bias, Y, zero16, cs, act_kind,
+                                         stats);
 }
 
 // ---------------------------------------------------------------------------
+// register-staged forward (GLDS: A by LDS-DMA, which needs the all-pow2
+// vector gate; B always through registers, scatter-transposed)
 template <typename T, bool POW2, bool GLDS>
 __launch_bounds__(THREADS)
 __global__ void k_conv_fwd(const T* __restrict__ X, const T* __restrict__ Wt,
-                           const float* __restrict__ bias_f32,
-                           const T* __restrict__ bias_t, T* __restrict__ Y,
+                           const T* __restrict__ bias, T* __restrict__ Y,
                            const T* __restrict__ zero16, ConvShape cs,
                            int act_kind) {
-  constexpr int V = 16 / sizeof(T);
+  static_assert(!GLDS || POW2, "the LDS-DMA gate implies an all-pow2 shape");
   __shared__ alignas(16) T As[BM * BK];
   __shared__ alignas(16) T Bs[BN * BK];
 
   const int M = cs.N * cs.OH * cs.OW;
   const int K = cs.KH * cs.KW * cs.Cin;
   int tm_, tn_;
-  // grouped tile ordering when the gathered activation stream exceeds
-  // the 256 MiB L3 across its Cout/BN re-reads (see tile_gemm.h)
-  if ((int64_t)cs.N * cs.OH * cs.OW * (cs.KH * cs.KW * cs.Cin) >
-      (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tm_, tn_);
-  else {
-    tm_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  conv_tile_order(cs, tm_, tn_);
   const int m0 = tm_ * BM;
   const int n0 = tn_ * BN;
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
-  using VecT = Pack16<T>;
 
   // fused-im2col source address for a 16B chunk (row, kk elem), or the
   // zero page when the chunk is out of image/padding/tail range; only
@@ -374,98 +591,26 @@ __global__ void k_conv_fwd(const T* __restrict__ X, const T* __restrict__ Wt,
   auto a_src = [&](int k0, int rl, int kk) -> const T* {
     int gm = m0 + rl, gk = k0 + kk;
     if (gm >= M || gk >= K) return zero16;
-    int n = idiv<POW2>(gm, cs.d_ohow);
-    int rem = gm - n * (cs.OH * cs.OW);
-    int oh = idiv<POW2>(rem, cs.d_ow), ow = rem - oh * cs.OW;
-    int ci = imod<POW2>(gk, cs.d_cin);
-    int kidx = idiv<POW2>(gk, cs.d_cin);
-    int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-    int ih = oh * cs.SH - cs.PH + kh;
-    int iw = ow * cs.SW - cs.PW + kw;
-    if (ih < 0 || ih >= cs.H || iw < 0 || iw >= cs.W) return zero16;
-    return &X[(((int64_t)n * cs.H + ih) * cs.W + iw) * cs.Cin + ci];
+    return fwd_src<POW2>(X, cs, fwd_row<POW2>(cs, gm), gk, zero16);
   };
 
   for (int k0 = 0; k0 < K; k0 += BK) {
     if constexpr (GLDS) {
       glds_stage_a<T>(As, wc, [&](int rl, int kk) { return a_src(k0, rl, kk); });
     } else {
-    // ---- stage A: im2col gather ----
-#pragma unroll
-    for (int c = threadIdx.x; c < BM * (BK / V); c += THREADS) {
-      int row = c / (BK / V);
-      int kk = (c % (BK / V)) * V;
-      int gm = m0 + row, gk = k0 + kk;
-      VecT v = {};
-      if (gm < M && gk < K) {
-        int n = idiv<POW2>(gm, cs.d_ohow);
-        int rem = gm - n * (cs.OH * cs.OW);
-        int oh = idiv<POW2>(rem, cs.d_ow), ow = rem - oh * cs.OW;
-        int ci = imod<POW2>(gk, cs.d_cin);
-        int kidx = idiv<POW2>(gk, cs.d_cin);
-        int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-        if (ci + V <= cs.Cin && gk + V <= K && (cs.Cin % V) == 0 &&
-            aligned16(X)) {
-          int ih = oh * cs.SH - cs.PH + kh;
-          int iw = ow * cs.SW - cs.PW + kw;
-          if (ih >= 0 && ih < cs.H && iw >= 0 && iw < cs.W)
-            v = *(const VecT*)&X[(((int64_t)n * cs.H + ih) * cs.W + iw) *
-                                     cs.Cin + ci];
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j) {
-            int k = gk + j;
-            if (k < K) {
-              int cij = imod<POW2>(k, cs.d_cin);
-              int kj = idiv<POW2>(k, cs.d_cin);
-              int kwj = kj % cs.KW, khj = kj / cs.KW;
-              int ih = oh * cs.SH - cs.PH + khj;
-              int iw = ow * cs.SW - cs.PW + kwj;
-              if (ih >= 0 && ih < cs.H && iw >= 0 && iw < cs.W)
-                v.e[j] = X[(((int64_t)n * cs.H + ih) * cs.W + iw) * cs.Cin + cij];
-            }
-          }
-        }
-      }
-      *(VecT*)&As[lds_off<T>(row, kk)] = v;
+      stage_a_gathered(As, m0, k0, M, K, [&](int gm, int gk) {
+        return fwd_gather16<POW2>(X, cs, fwd_row<POW2>(cs, gm), gk, K);
+      });
     }
-    }
-    // ---- stage B (weights [K, Cout]) -> Bs[n][k] scatter-transpose ----
-#pragma unroll
-    for (int c = threadIdx.x; c < BK * (BN / V); c += THREADS) {
-      int kk = c / (BN / V);
-      int nn = (c % (BN / V)) * V;
-      int gk = k0 + kk, gn = n0 + nn;
-      VecT v = {};
-      if (gk < K) {
-        const T* src = &Wt[(int64_t)gk * cs.Cout + gn];
-        if (gn + V <= cs.Cout && aligned16(src)) {
-          v = *(const VecT*)src;
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j)
-            if (gn + j < cs.Cout) v.e[j] = Wt[(int64_t)gk * cs.Cout + gn + j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        Bs[lds_off<T>(nn + j, kk)] = v.e[j];
-    }
+    // weights [K, Cout] -> Bs[n][k]
+    stage_b_transposed(
+        Bs, [&](int gk) { return &Wt[(int64_t)gk * cs.Cout]; }, cs.Cout, n0,
+        k0, K);
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
     __syncthreads();
   }
-
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < cs.Cout) {
-      if (bias_f32) v += bias_f32[col];
-      if (bias_t) v += VecIO<T>::to_f32(bias_t[col]);
-      if (act_kind != ACT_LINEAR) v = act_apply(v, act_kind);
-      Y[(int64_t)row * cs.Cout + col] = VecIO<T>::from_f32(v);
-    }
-  });
+  conv_fwd_store(wc, acc, bias, Y, cs, act_kind, m0, n0, M);
 }
 
 // ---------------------------------------------------------------------------
@@ -478,208 +623,92 @@ __launch_bounds__(THREADS)
 __global__ void k_conv_dgrad(const T* __restrict__ DY, const T* __restrict__ WT,
                              T* __restrict__ DX, const T* __restrict__ zero16,
                              ConvShape cs) {
+  static_assert(!GLDS || POW2, "the LDS-DMA gate implies an all-pow2 shape");
+  static_assert(GLDS || !(S2 || S1), "stride routes are LDS-DMA only");
   constexpr int V = 16 / sizeof(T);
   __shared__ alignas(16) T As[BM * BK];
   __shared__ alignas(16) T Bs[BN * BK];
 
-  // S2: stride-2 parity decomposition. blockIdx.z selects the
-  // (ih%2, iw%2) class so every (kh,kw) visited satisfies the stride
-  // divisibility test by construction -- the generic kernel at stride 2
-  // burns 3/4 of its MFMAs multiplying gathered zeros. The launcher
-  // rewrites cs.d_hw/d_w to the per-class (Hc*Wc, Wc) divisors.
-  const int cls_a = S2 ? ((int)blockIdx.z >> 1) : 0;
-  const int cls_b = S2 ? ((int)blockIdx.z & 1) : 0;
-  const int start_h = S2 ? ((cls_a + cs.PH) & 1) : 0;
-  const int start_w = S2 ? ((cls_b + cs.PW) & 1) : 0;
-  const int nkh = S2 ? ((cs.KH - start_h + 1) >> 1) : cs.KH;
-  const int nkw = S2 ? ((cs.KW - start_w + 1) >> 1) : cs.KW;
-  const int Hc = S2 ? (cs.H >> 1) : cs.H;
-  const int Wc = S2 ? (cs.W >> 1) : cs.W;
-  const int M = cs.N * Hc * Wc;
-  const int K = nkh * nkw * cs.Cout;
+  const DgradClass<S2> dc(cs);
+  const int M = dc.M, K = dc.K;
   int tm_, tn_;
-  // grouped tile ordering when the gathered activation stream exceeds
-  // the 256 MiB L3 across its Cout/BN re-reads (see tile_gemm.h)
-  if ((int64_t)cs.N * cs.OH * cs.OW * (cs.KH * cs.KW * cs.Cin) >
-      (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tm_, tn_);
-  else {
-    tm_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  conv_tile_order(cs, tm_, tn_);
   const int m0 = tm_ * BM;
   const int n0 = tn_ * BN;
   const WaveCoord wc;
   f32x4 acc[FM][FN] = {};
-  using VecT = Pack16<T>;
 
+  // dy element (gm, gk), gk = (tap, co) of this class; oob in the padding
+  // and where the stride does not divide
+  auto src = [&](int gm, int gk, const T* oob) {
+    int n, ih, iw;
+    dc.template coords<POW2>(cs, gm, n, ih, iw);
+    int co = imod<POW2>(gk, cs.d_cout);
+    const DgradTap t = dc.tap(cs, idiv<POW2>(gk, cs.d_cout));
+    return dgrad_src<S2, S1>(DY, cs, n, ih, iw, t.kh, t.kw, co, oob);
+  };
   auto a_src = [&](int k0, int rl, int kk) -> const T* {
     int gm = m0 + rl, gk = k0 + kk;
     if (gm >= M || gk >= K) return zero16;
-    int n = idiv<POW2>(gm, cs.d_hw);
-    int rem = gm - n * (Hc * Wc);
-    int ih = idiv<POW2>(rem, cs.d_w), iw = rem - ih * Wc;
-    int co = imod<POW2>(gk, cs.d_cout);
-    int kidx = idiv<POW2>(gk, cs.d_cout);
-    if constexpr (S2) {
-      ih = 2 * ih + cls_a;
-      iw = 2 * iw + cls_b;
-      int kwi = kidx & (nkw - 1);              // nkw is 1 or 2
-      int khi = nkw == 2 ? (kidx >> 1) : kidx;
-      int kh = start_h + 2 * khi, kw = start_w + 2 * kwi;
-      int th = ih + cs.PH - kh, tw = iw + cs.PW - kw;
-      if (th < 0 || tw < 0) return zero16;
-      int oh = th >> 1, ow = tw >> 1;          // divisible by construction
-      if (oh >= cs.OH || ow >= cs.OW) return zero16;
-      return &DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) * cs.Cout + co];
-    } else {
-      int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-      int th = ih + cs.PH - kh, tw = iw + cs.PW - kw;
-      if constexpr (S1) {  // stride 1: no divisibility test, oh == th
-        if (th < 0 || tw < 0 || th >= cs.OH || tw >= cs.OW) return zero16;
-        return &DY[(((int64_t)n * cs.OH + th) * cs.OW + tw) * cs.Cout + co];
-      } else {
-        if (th < 0 || tw < 0 || th % cs.SH || tw % cs.SW) return zero16;
-        int oh = th / cs.SH, ow = tw / cs.SW;
-        if (oh >= cs.OH || ow >= cs.OW) return zero16;
-        return &DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) * cs.Cout + co];
-      }
-    }
+    return src(gm, gk, zero16);
   };
 
   for (int k0 = 0; k0 < K; k0 += BK) {
     if constexpr (GLDS) {
       glds_stage_a<T>(As, wc, [&](int rl, int kk) { return a_src(k0, rl, kk); });
     } else {
-    // ---- stage A: gather dy with stride/padding inversion ----
-#pragma unroll
-    for (int c = threadIdx.x; c < BM * (BK / V); c += THREADS) {
-      int row = c / (BK / V);
-      int kk = (c % (BK / V)) * V;
-      int gm = m0 + row, gk = k0 + kk;
-      VecT v = {};
-      if (gm < M && gk < K) {
-        int n = idiv<POW2>(gm, cs.d_hw);
-        int rem = gm - n * (cs.H * cs.W);
-        int ih = idiv<POW2>(rem, cs.d_w), iw = rem - ih * cs.W;
-        int co = imod<POW2>(gk, cs.d_cout);
-        int kidx = idiv<POW2>(gk, cs.d_cout);
-        int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-        auto gather_one = [&](int khj, int kwj, int coj) -> T {
-          int th = ih + cs.PH - khj, tw = iw + cs.PW - kwj;
-          if (th < 0 || tw < 0 || th % cs.SH || tw % cs.SW) return T(0.0f);
-          int oh = th / cs.SH, ow = tw / cs.SW;
-          if (oh >= cs.OH || ow >= cs.OW) return T(0.0f);
-          return DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) * cs.Cout + coj];
-        };
-        if (co + V <= cs.Cout && gk + V <= K && (cs.Cout % V) == 0 &&
-            aligned16(DY)) {
-          int th = ih + cs.PH - kh, tw = iw + cs.PW - kw;
-          if (th >= 0 && tw >= 0 && th % cs.SH == 0 && tw % cs.SW == 0) {
-            int oh = th / cs.SH, ow = tw / cs.SW;
-            if (oh < cs.OH && ow < cs.OW)
-              v = *(const VecT*)&DY[(((int64_t)n * cs.OH + oh) * cs.OW + ow) *
-                                        cs.Cout + co];
-          }
+      // gather dy with stride/padding inversion: one vector load when the
+      // run lies in one (kh,kw) slice, else element-wise
+      stage_a_gathered(As, m0, k0, M, K, [&](int gm, int gk) {
+        Pack16<T> v = {};
+        if (imod<POW2>(gk, cs.d_cout) + V <= cs.Cout && gk + V <= K &&
+            (cs.Cout % V) == 0 && aligned16(DY)) {
+          if (const T* p = src(gm, gk, nullptr)) v = *(const Pack16<T>*)p;
         } else {
 #pragma unroll
           for (int j = 0; j < V; ++j) {
-            int k = gk + j;
-            if (k < K) {
-              int coj = imod<POW2>(k, cs.d_cout);
-              int kj = idiv<POW2>(k, cs.d_cout);
-              v.e[j] = gather_one(kj / cs.KW, kj % cs.KW, coj);
-            }
+            if (gk + j >= K) continue;
+            if (const T* p = src(gm, gk + j, nullptr)) v.e[j] = *p;
           }
         }
-      }
-      *(VecT*)&As[lds_off<T>(row, kk)] = v;
+        return v;
+      });
     }
-    }
-    // ---- stage B (w_t [KH*KW*Cout, Cin]) -> Bs[ci][k] ----
-#pragma unroll
-    for (int c = threadIdx.x; c < BK * (BN / V); c += THREADS) {
-      int kk = c / (BN / V);
-      int nn = (c % (BN / V)) * V;
-      int gk = k0 + kk, gn = n0 + nn;
-      VecT v = {};
-      if (gk < K) {
-        int64_t wrow = gk;
-        if constexpr (S2) {
-          // compacted (khi,kwi,co) -> full (kh*KW+kw)*Cout+co row of WT
-          int co = imod<POW2>(gk, cs.d_cout);
-          int kidx = idiv<POW2>(gk, cs.d_cout);
-          int kwi = kidx & (nkw - 1);
-          int khi = nkw == 2 ? (kidx >> 1) : kidx;
-          wrow = (int64_t)((start_h + 2 * khi) * cs.KW + start_w + 2 * kwi) *
-                     cs.Cout + co;
-        }
-        const T* src = &WT[wrow * cs.Cin + gn];
-        if (gn + V <= cs.Cin && aligned16(src)) {
-          v = *(const VecT*)src;
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j)
-            if (gn + j < cs.Cin) v.e[j] = src[j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        Bs[lds_off<T>(nn + j, kk)] = v.e[j];
-    }
+    // w_t [KH*KW*Cout, Cin] -> Bs[ci][k]; a class's compacted k index maps
+    // to the full (kh*KW+kw)*Cout+co row
+    stage_b_transposed(
+        Bs,
+        [&](int gk) {
+          int64_t wrow = gk;
+          if constexpr (S2)
+            wrow = (int64_t)dc.tap(cs, idiv<POW2>(gk, cs.d_cout)).widx *
+                       cs.Cout + imod<POW2>(gk, cs.d_cout);
+          return &WT[wrow * cs.Cin];
+        },
+        cs.Cin, n0, k0, K);
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
     __syncthreads();
   }
-
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < cs.Cin) {
-      int64_t pix = row;
-      if constexpr (S2) {
-        int n = idiv<POW2>(row, cs.d_hw);
-        int rem = row - n * (Hc * Wc);
-        int ihp = idiv<POW2>(rem, cs.d_w);
-        int ih = 2 * ihp + cls_a, iw = 2 * (rem - ihp * Wc) + cls_b;
-        pix = ((int64_t)n * cs.H + ih) * cs.W + iw;
-      }
-      DX[pix * cs.Cin + col] = VecIO<T>::from_f32(v);
-    }
-  });
+  dgrad_store<POW2>(wc, acc, DX, cs, dc, m0, n0);
 }
 
 // ---------------------------------------------------------------------------
-// double-buffered pure-glds dgrad (see k_conv_fwd_db): the weight comes
-// pre-transposed to [Cin, KH*KW*Cout] so B rows are k-contiguous; with S2
-// the compacted parity-class k index remaps into the full column space.
-template <typename T, bool POW2, bool S2 = false, bool S1 = false>
+// double-buffered pure-glds dgrad (see k_conv_fwd_db; all-pow2 shapes only):
+// the weight comes pre-transposed to [Cin, KH*KW*Cout] so B rows are
+// k-contiguous; with S2 the compacted parity-class k index remaps into the
+// full column space.
+template <typename T, bool S2 = false, bool S1 = false>
 __launch_bounds__(THREADS)
 __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
                                 const T* __restrict__ WT2D,
                                 T* __restrict__ DX,
                                 const T* __restrict__ zero16, ConvShape cs) {
-  const int cls_a = S2 ? ((int)blockIdx.z >> 1) : 0;
-  const int cls_b = S2 ? ((int)blockIdx.z & 1) : 0;
-  const int start_h = S2 ? ((cls_a + cs.PH) & 1) : 0;
-  const int start_w = S2 ? ((cls_b + cs.PW) & 1) : 0;
-  const int nkh = S2 ? ((cs.KH - start_h + 1) >> 1) : cs.KH;
-  const int nkw = S2 ? ((cs.KW - start_w + 1) >> 1) : cs.KW;
-  const int Hc = S2 ? (cs.H >> 1) : cs.H;
-  const int Wc = S2 ? (cs.W >> 1) : cs.W;
-  const int M = cs.N * Hc * Wc;
-  const int K = nkh * nkw * cs.Cout;
+  const DgradClass<S2> dc(cs);
+  const int M = dc.M, K = dc.K;
   const int KFULL = cs.KH * cs.KW * cs.Cout;
   int tm_, tn_;
-  // grouped tile ordering when the gathered activation stream exceeds
-  // the 256 MiB L3 across its Cout/BN re-reads (see tile_gemm.h)
-  if ((int64_t)cs.N * cs.OH * cs.OW * (cs.KH * cs.KW * cs.Cin) >
-      (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tm_, tn_);
-  else {
-    tm_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  conv_tile_order(cs, tm_, tn_);
   const int m0 = tm_ * BM;
   const int n0 = tn_ * BN;
   const WaveCoord wc;
@@ -694,12 +723,12 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
       // d_hw / d_w hold the per-class (Hc*Wc, Wc) divisors under S2
       [&](int gm, int64_t& noff, int& p, int& q) {
         const int n = gm >> cs.d_hw.lg;
-        const int rem = gm & (Hc * Wc - 1);
-        int ih = rem >> cs.d_w.lg, iw = rem & (Wc - 1);
+        const int rem = gm & (dc.Hc * dc.Wc - 1);
+        int ih = rem >> cs.d_w.lg, iw = rem & (dc.Wc - 1);
         if constexpr (S2) {
           // th = ih + PH - kh is even by construction: oh = p - khi
-          p = (2 * ih + cls_a + cs.PH - start_h) >> 1;
-          q = (2 * iw + cls_b + cs.PW - start_w) >> 1;
+          p = (2 * ih + dc.cls_a + cs.PH - dc.start_h) >> 1;
+          q = (2 * iw + dc.cls_b + cs.PW - dc.start_w) >> 1;
         } else {
           p = ih + cs.PH;
           q = iw + cs.PW;
@@ -712,12 +741,10 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
         c = gk & (cs.Cout - 1);
         if constexpr (S2) {
           // compacted (khi,kwi,co) -> full (kh*KW+kw)*Cout+co column
-          const int kwi = kidx & (nkw - 1);              // nkw is 1 or 2
-          const int khi = nkw == 2 ? (kidx >> 1) : kidx;
-          dh = khi;
-          dw = kwi;
-          bcol = (((start_h + 2 * khi) * cs.KW + start_w + 2 * kwi)
-                  << cs.d_cout.lg) + c;
+          const DgradTap t = dc.tap(cs, kidx);
+          dh = t.khi;
+          dw = t.kwi;
+          bcol = (t.widx << cs.d_cout.lg) + c;
         } else {
           kdecode(kidx, cs, dh, dw);
           bcol = gk;
@@ -737,20 +764,7 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
                  ow * cs.SW == tw && oh < cs.OH && ow < cs.OW;
         }
       });
-
-  epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
-    if (row < M && col < cs.Cin) {
-      int64_t pix = row;
-      if constexpr (S2) {
-        int n = idiv<POW2>(row, cs.d_hw);
-        int rem = row - n * (Hc * Wc);
-        int ihp = idiv<POW2>(rem, cs.d_w);
-        int ih = 2 * ihp + cls_a, iw = 2 * (rem - ihp * Wc) + cls_b;
-        pix = ((int64_t)n * cs.H + ih) * cs.W + iw;
-      }
-      DX[pix * cs.Cin + col] = VecIO<T>::from_f32(v);
-    }
-  });
+  dgrad_store<true>(wc, acc, DX, cs, dc, m0, n0);
 }
 
 // ---------------------------------------------------------------------------
@@ -769,15 +783,8 @@ __global__ void k_conv_wgrad(const T* __restrict__ X, const T* __restrict__ DY,
   const int M = cs.N * cs.OH * cs.OW;         // reduction dim
   const int Kout = cs.KH * cs.KW * cs.Cin;    // output rows
   int tr_, tn_;
-  // same grouped ordering: the gathered-x A operand [Kout, M] is
-  // re-read gridDim.y times without it
-  if ((int64_t)(cs.KH * cs.KW * cs.Cin) * cs.N * cs.OH * cs.OW >
-      (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tr_, tn_);
-  else {
-    tr_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  // the gathered-x A operand [Kout, M] is re-read gridDim.y times
+  conv_tile_order(cs, tr_, tn_);
   const int r0 = tr_ * BM;
   const int n0 = tn_ * BN;
   const int m_begin = (int)((int64_t)M * blockIdx.z / gridDim.z);
@@ -788,7 +795,6 @@ __global__ void k_conv_wgrad(const T* __restrict__ X, const T* __restrict__ DY,
   // the columns of its dy tiles and writes them as slab row Kout
   const bool colsum = bias_row && tr_ == 0;
   float bsum = 0.0f;
-  using VecT = Pack16<T>;
 
   for (int k0 = m_begin; k0 < m_end; k0 += BK) {
     // ---- stage A^T: x rows ci-contiguous, scatter into As[ko][m] ----
@@ -798,92 +804,42 @@ __global__ void k_conv_wgrad(const T* __restrict__ X, const T* __restrict__ DY,
       int rr = (c % (BM / V)) * V;
       int gm = k0 + mm;
       int gr = r0 + rr;
-      VecT v = {};
-      if (gm < m_end && gr < Kout) {
-        int n = idiv<POW2>(gm, cs.d_ohow);
-        int rem = gm - n * (cs.OH * cs.OW);
-        int oh = idiv<POW2>(rem, cs.d_ow), ow = rem - oh * cs.OW;
-        int ci = imod<POW2>(gr, cs.d_cin);
-        int kidx = idiv<POW2>(gr, cs.d_cin);
-        int kh, kw;
-    kdecode(kidx, cs, kh, kw);
-        if (ci + V <= cs.Cin && gr + V <= Kout && (cs.Cin % V) == 0 &&
-            aligned16(X)) {
-          int ih = oh * cs.SH - cs.PH + kh;
-          int iw = ow * cs.SW - cs.PW + kw;
-          if (ih >= 0 && ih < cs.H && iw >= 0 && iw < cs.W)
-            v = *(const VecT*)&X[(((int64_t)n * cs.H + ih) * cs.W + iw) *
-                                     cs.Cin + ci];
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j) {
-            int r = gr + j;
-            if (r < Kout) {
-              int cij = imod<POW2>(r, cs.d_cin);
-              int kj = idiv<POW2>(r, cs.d_cin);
-              int kwj = kj % cs.KW, khj = kj / cs.KW;
-              int ih = oh * cs.SH - cs.PH + khj;
-              int iw = ow * cs.SW - cs.PW + kwj;
-              if (ih >= 0 && ih < cs.H && iw >= 0 && iw < cs.W)
-                v.e[j] = X[(((int64_t)n * cs.H + ih) * cs.W + iw) * cs.Cin + cij];
-            }
-          }
-        }
-      }
+      Pack16<T> v = {};
+      if (gm < m_end && gr < Kout)
+        v = fwd_gather16<POW2>(X, cs, fwd_row<POW2>(cs, gm), gr, Kout);
 #pragma unroll
       for (int j = 0; j < V; ++j)
         As[lds_off<T>(rr + j, mm)] = v.e[j];
     }
-    // ---- stage B: dy[m][co] -> Bs[co][m] ----
-#pragma unroll
-    for (int c = threadIdx.x; c < BK * (BN / V); c += THREADS) {
-      int mm = c / (BN / V);
-      int nn = (c % (BN / V)) * V;
-      int gm = k0 + mm;
-      int gn = n0 + nn;
-      VecT v = {};
-      if (gm < m_end) {
-        const T* src = &DY[(int64_t)gm * cs.Cout + gn];
-        if (gn + V <= cs.Cout && aligned16(src)) {
-          v = *(const VecT*)src;
-        } else {
-#pragma unroll
-          for (int j = 0; j < V; ++j)
-            if (gn + j < cs.Cout) v.e[j] = DY[(int64_t)gm * cs.Cout + gn + j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < V; ++j)
-        Bs[lds_off<T>(nn + j, mm)] = v.e[j];
-    }
+    // dy[m][co] -> Bs[co][m]
+    stage_b_transposed(
+        Bs, [&](int gm) { return &DY[(int64_t)gm * cs.Cout]; }, cs.Cout, n0,
+        k0, m_end);
     __syncthreads();
     mfma_compute_tile(As, Bs, wc, acc);
     if (colsum) bsum += colsum_tile_partial(Bs);
     __syncthreads();
   }
-
-  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
-  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
-    if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
-  });
-  if (colsum) {
-    bsum = colsum_tile_finish(bsum);
-    int col = n0 + (threadIdx.x >> 2);
-    if ((threadIdx.x & 3) == 0 && col < cs.Cout)
-      out[(int64_t)Kout * cs.Cout + col] = bsum;
-  }
+  float* out = wgrad_slab_store(wc, acc, DW, cs, Kout, bias_row, r0, n0);
+  if (colsum) wgrad_colsum_store(out, cs, Kout, n0, bsum);
 }
 
 // ---------------------------------------------------------------------------
-// vector-guaranteed wgrad (Cin%V==0, Cout%V==0, 16B-aligned tensors): stages
-// in three phases -- addresses (zero-page for OOB/padding), then all 16B
-// loads, then the LDS scatter -- so RA+RB global loads stay in flight.
+// vector-guaranteed wgrad (all-pow2 shape, Cin%V==0, Cout%V==0, 16B-aligned
+// tensors; fp32 only -- bf16 takes k_conv_wgrad_tr): stages in three phases
+// -- addresses (zero-page for OOB/padding), then all 16B loads, then the LDS
+// scatter -- so RA+RB global loads stay in flight.
 // The generic kernel's `#pragma unroll 1` staging (needed there to avoid
 // 221-256 VGPR spills from per-iteration gather state) serializes to one
 // load in flight per wave; holding only pointers between phases keeps the
 // live state at ~24 VGPR.
+// Software-pipelined (T14 rotate): tile t's registers are written to LDS,
+// then tile t+1's loads are ISSUED into the same (now dead) registers before
+// tile t's MFMA phase -- the gather latency lands under the MFMAs instead of
+// being exposed at the head of every chunk (the attention kernels' TStage
+// split, applied here).
 // ---------------------------------------------------------------------------
-template <typename T, bool POW2>
+template <typename T>
 __launch_bounds__(THREADS, 3)
 __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
                                  const T* __restrict__ DY,
@@ -898,15 +854,7 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
   const int M = cs.N * cs.OH * cs.OW;
   const int Kout = cs.KH * cs.KW * cs.Cin;
   int tr_, tn_;
-  // same grouped ordering: the gathered-x A operand [Kout, M] is
-  // re-read gridDim.y times without it
-  if ((int64_t)(cs.KH * cs.KW * cs.Cin) * cs.N * cs.OH * cs.OW >
-      (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tr_, tn_);
-  else {
-    tr_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  conv_tile_order(cs, tr_, tn_);
   const int r0 = tr_ * BM;
   const int n0 = tn_ * BN;
   const int m_begin = (int)((int64_t)M * blockIdx.z / gridDim.z);
@@ -917,56 +865,18 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
   float bsum = 0.0f;
   using VecT = Pack16<T>;
 
-  // bf16: each thread owns one 8-row group x 4 consecutive m columns --
-  // after the loads an in-thread 8x4 transpose packs 4 m-values per row
-  // into one 8B ds_write_b64 (vs 8x ds_write_b16 per load; LDS
-  // instruction issue was wgrad's post-phase-separation bottleneck:
-  // 48 b16 writes vs 16 MFMAs per thread-chunk). The XOR swizzle flips
-  // byte bits 4-6 only, so the 8B alignment survives. fp32 keeps the
-  // generic scatter.
-  //
-  // Software-pipelined (T14 rotate): tile t's registers are written to
-  // LDS, then tile t+1's loads are ISSUED into the same (now dead)
-  // registers before tile t's MFMA phase — the gather latency lands
-  // under the MFMAs instead of being exposed at the head of every
-  // chunk (the attention kernels' TStage split, applied here).
-  constexpr bool TR = sizeof(T) == 2;
-  // lane mapping: consecutive lanes share the m-quad and span the row
-  // groups: the 16 lanes' 16B global loads form one contiguous 256B run
-  // (the conflict-free same-row/mm-strided write mapping was tried and
-  // lost more to broken global coalescing than its bank relief won)
-  const int a_rr = TR ? (threadIdx.x & (BM / V - 1)) * V : 0;
-  const int a_mm0 = TR ? (threadIdx.x / (BM / V)) * 4 : 0;
   VecT va[RA], vb[RB];
   auto load_tile = [&](int k0) {
     const T* asrc[RA];
 #pragma unroll
     for (int it = 0; it < RA; ++it) {
-      int mm, rr;
-      if constexpr (TR) {
-        mm = a_mm0 + it;
-        rr = a_rr;
-      } else {
-        int c = threadIdx.x + it * THREADS;
-        mm = c / (BM / V);
-        rr = (c % (BM / V)) * V;
-      }
+      int c = threadIdx.x + it * THREADS;
+      int mm = c / (BM / V);
+      int rr = (c % (BM / V)) * V;
       int gm = k0 + mm, gr = r0 + rr;
-      const T* p = zero16;
-      if (gm < m_end && gr < Kout) {
-        int n = idiv<POW2>(gm, cs.d_ohow);
-        int rem = gm - n * (cs.OH * cs.OW);
-        int oh = idiv<POW2>(rem, cs.d_ow), ow = rem - oh * cs.OW;
-        int ci = imod<POW2>(gr, cs.d_cin);
-        int kidx = idiv<POW2>(gr, cs.d_cin);
-        int kh, kw;
-        kdecode(kidx, cs, kh, kw);
-        int ih = oh * cs.SH - cs.PH + kh;
-        int iw = ow * cs.SW - cs.PW + kw;
-        if (ih >= 0 && ih < cs.H && iw >= 0 && iw < cs.W)
-          p = &X[(((int64_t)n * cs.H + ih) * cs.W + iw) * cs.Cin + ci];
-      }
-      asrc[it] = p;
+      asrc[it] = gm < m_end && gr < Kout
+                     ? fwd_src<true>(X, cs, fwd_row<true>(cs, gm), gr, zero16)
+                     : zero16;
     }
     const T* bsrc[RB];
 #pragma unroll
@@ -987,23 +897,13 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
 
   load_tile(m_begin);
   for (int k0 = m_begin; k0 < m_end; k0 += BK) {
-    if constexpr (TR) {
 #pragma unroll
-      for (int j = 0; j < V; ++j) {
-        struct alignas(8) H4 { T e[4]; } h;
+    for (int it = 0; it < RA; ++it) {
+      int c = threadIdx.x + it * THREADS;
+      int mm = c / (BM / V);
+      int rr = (c % (BM / V)) * V;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) h.e[q] = va[q].e[j];
-        *(H4*)&As[lds_off<T>(a_rr + j, a_mm0)] = h;
-      }
-    } else {
-#pragma unroll
-      for (int it = 0; it < RA; ++it) {
-        int c = threadIdx.x + it * THREADS;
-        int mm = c / (BM / V);
-        int rr = (c % (BM / V)) * V;
-#pragma unroll
-        for (int j = 0; j < V; ++j) As[lds_off<T>(rr + j, mm)] = va[it].e[j];
-      }
+      for (int j = 0; j < V; ++j) As[lds_off<T>(rr + j, mm)] = va[it].e[j];
     }
 #pragma unroll
     for (int it = 0; it < RB; ++it) {
@@ -1019,17 +919,8 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
     if (colsum) bsum += colsum_tile_partial(Bs);
     __syncthreads();
   }
-
-  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
-  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
-    if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
-  });
-  if (colsum) {
-    bsum = colsum_tile_finish(bsum);
-    int col = n0 + (threadIdx.x >> 2);
-    if ((threadIdx.x & 3) == 0 && col < cs.Cout)
-      out[(int64_t)Kout * cs.Cout + col] = bsum;
-  }
+  float* out = wgrad_slab_store(wc, acc, DW, cs, Kout, bias_row, r0, n0);
+  if (colsum) wgrad_colsum_store(out, cs, Kout, n0, bsum);
 }
 
 // ---------------------------------------------------------------------------
@@ -1041,7 +932,7 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
 // (tile_gemm.h, kmaj_off / tr_frag_issue). A lane's slot in each of its DMA
 // instructions never moves, so its (kh,kw,ci) decode is hoisted out of the
 // k-loop; per chunk only the (n,oh,ow) decode of its m-rows remains.
-// Same gate as k_conv_wgrad_vec<bf16>: all-pow2 shape, Cin%8 == Cout%8 == 0,
+// Same gate as k_conv_wgrad_vec: all-pow2 shape, Cin%8 == Cout%8 == 0,
 // 16B-aligned tensors. Double-buffered k-loop (48 KB LDS, 3 blocks/CU): it
 // measured 3-5% ahead of the single-buffer form (24 KB) on the WRN shapes.
 // ---------------------------------------------------------------------------
@@ -1059,12 +950,7 @@ __global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
   const int M = cs.N * cs.OH * cs.OW;
   const int Kout = cs.KH * cs.KW * cs.Cin;
   int tr_, tn_;
-  if ((int64_t)Kout * M > (int64_t)32 * 1024 * 1024)
-    tile::tile_remap_xcd<4>(tr_, tn_);
-  else {
-    tr_ = blockIdx.x;
-    tn_ = blockIdx.y;
-  }
+  conv_tile_order(cs, tr_, tn_);
   const int r0 = tr_ * BM;
   const int n0 = tn_ * BN;
   const int m_begin = (int)((int64_t)M * blockIdx.z / gridDim.z);
@@ -1164,10 +1050,7 @@ __global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
     if (k0 + BK < m_end) step(k0 + BK, As1, Bs1, As0, Bs0);
   }
 
-  float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
-  epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
-    if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
-  });
+  float* out = wgrad_slab_store(wc, acc, DW, cs, Kout, bias_row, r0, n0);
   if (colsum && wc.lane < 16) {
     // every row of bacc is the column sum; lanes 0-15 hold row 0
     int col = n0 + wc.wcol0 + 16 * wm + wc.lane;
@@ -1236,48 +1119,97 @@ __global__ void k_transpose_w_dgrad_vec(const T* __restrict__ W,
 }
 
 // ---------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------
 static bool all_pow2(const ConvShape& cs) {
   return cs.d_ohow.lg >= 0 && cs.d_ow.lg >= 0 && cs.d_cin.lg >= 0 &&
          cs.d_hw.lg >= 0 && cs.d_w.lg >= 0 && cs.d_cout.lg >= 0;
 }
 
-// k-loop length up to which the double buffer is used (TNN_DB_MAXK, read
-// once). Past it bf16 takes the single-buffer form of the same DMA-staged
-// tile; fp32 falls back to k_conv_fwd.
+// 16-byte vector / LDS-DMA access to an NHWC tensor with this many channels
+static bool vec_ok(DT dt, const void* ptr, int channels) {
+  return channels % vec_elems(dt) == 0 && ptr_aligned16(ptr);
+}
+
+// integer environment switch (callers read it once)
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// TNN_FWD_DB=0 routes fwd and dgrad back to the register-staged /
+// single-buffer kernels, so both can be compared from one build
+static bool db_on() {
+  static const bool on = env_int("TNN_FWD_DB", 1) != 0;
+  return on;
+}
+
+// k-loop length up to which the forward double buffer is used. Past it bf16
+// takes the single-buffer form of the same DMA-staged tile; fp32 falls back
+// to k_conv_fwd.
 static int fwd_db_maxk() {
-  static const int maxk = []() {
-    const char* e = getenv("TNN_DB_MAXK");
-    return e ? atoi(e) : 2304;
-  }();
+  static const int maxk = env_int("TNN_DB_MAXK", 2304);
   return maxk;
+}
+
+template <typename... KArgs, typename... Args>
+static void launch(void (*kern)(KArgs...), dim3 grid, hipStream_t s,
+                   Args... args) {
+  hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, args...);
 }
 
 // true: the launcher wants the [Cout][K] weight and takes a DMA-staged
 // kernel, which also carries the fused statistics epilogue
 bool conv2d_fwd_wants_db(DT dt, const void* x, const ConvShape& cs) {
-  static const bool db_on = []() {
-    const char* e = getenv("TNN_FWD_DB");
-    return !(e && atoi(e) == 0);
-  }();
-  if (!db_on) return false;
-  int v = dt == DT::F32 ? 4 : 8;
+  if (!db_on()) return false;
   if (dt == DT::F32 && cs.KH * cs.KW * cs.Cin > fwd_db_maxk()) return false;
-  return all_pow2(cs) && cs.Cin % v == 0 && (((uintptr_t)x & 15) == 0);
+  return all_pow2(cs) && vec_ok(dt, x, cs.Cin);
+}
+
+// out[b][c][r] = in[b][r][c]
+static void transpose2d_launch(DT dt, const void* in, void* out, int batch,
+                               int rows, int cols, hipStream_t s) {
+  dim3 grid((cols + 31) / 32, (rows + 31) / 32, batch);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(k_transpose2d_tiled<T>, grid, dim3(256), 0, s,
+                       (const T*)in, (T*)out, rows, cols);
+  });
 }
 
 void transpose_w_fwd_launch(DT dt, const void* w, void* w_t2, int KHW, int Cin,
                             int Cout, hipStream_t s) {
   // [KHW*Cin, Cout] -> [Cout, KHW*Cin] is a plain 2D transpose
-  int rows = KHW * Cin;
-  dim3 grid((Cout + 31) / 32, (rows + 31) / 32, 1);
-  if (dt == DT::F32)
-    hipLaunchKernelGGL(k_transpose2d_tiled<float>, grid, dim3(256), 0, s,
-                       (const float*)w, (float*)w_t2, rows, Cout);
-  else
-    hipLaunchKernelGGL(k_transpose2d_tiled<bf16>, grid, dim3(256), 0, s,
-                       (const bf16*)w, (bf16*)w_t2, rows, Cout);
+  transpose2d_launch(dt, w, w_t2, 1, KHW * Cin, Cout, s);
 }
 
+void transpose_w_launch(DT dt, const void* w, void* w_t, int KH, int KW,
+                        int Cin, int Cout, hipStream_t s) {
+  // batched [Cin, Cout] -> [Cout, Cin] transpose per (kh,kw) slice
+  transpose2d_launch(dt, w, w_t, KH * KW, Cin, Cout, s);
+}
+
+void transpose_w_dgrad_launch(DT dt, const void* w, void* w_t2d, int KHW,
+                              int Cin, int Cout, hipStream_t s) {
+  const bool vec = vec_ok(dt, w, Cout);
+  int64_t n = (int64_t)KHW * Cin * (vec ? Cout / vec_elems(dt) : Cout);
+  int blocks = (int)((n + 255) / 256);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto kern = vec ? k_transpose_w_dgrad_vec<T> : k_transpose_w_dgrad<T>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, (const T*)w,
+                       (T*)w_t2d, KHW, Cin, Cout);
+  });
+}
+
+// Route, first match (K = KH*KW*Cin; w_t2 is passed iff conv2d_fwd_wants_db:
+// switch on, all-pow2, vector gate, and for fp32 K <= TNN_DB_MAXK):
+//   w_t2, bf16, K > TNN_DB_MAXK   k_conv_fwd_sb<stats>
+//   w_t2                          k_conv_fwd_db<T, stats>
+//   all-pow2 and vector gate      k_conv_fwd<T, true, true>    (A by LDS-DMA)
+//   all-pow2                      k_conv_fwd<T, true, false>
+//   otherwise                     k_conv_fwd<T, false, false>
+// stats is honoured on the w_t2 routes only.
 void conv2d_fwd_launch(DT dt, const void* x, const void* w, const void* w_t2,
                        const void* bias, void* y, const void* zero16,
                        float* stats, const ConvShape& cs, bool relu,
@@ -1286,102 +1218,57 @@ void conv2d_fwd_launch(DT dt, const void* x, const void* w, const void* w_t2,
   dim3 grid(ceil_div(M, BM), ceil_div(cs.Cout, BN));
   int act = relu ? ACT_RELU : ACT_LINEAR;
   bool p2 = all_pow2(cs);
-  if (dt == DT::F32) {
+  bool g = p2 && vec_ok(dt, x, cs.Cin);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto X = (const T*)x;
+    auto B = (const T*)bias;
+    auto Y = (T*)y;
+    auto Z = (const T*)zero16;
     if (w_t2) {
-      auto kern = stats ? k_conv_fwd_db<float, true, true>
-                        : k_conv_fwd_db<float, true>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const float*)x,
-                         (const float*)w_t2, (const float*)bias,
-                         (const float*)nullptr, (float*)y,
-                         (const float*)zero16, cs, act, stats);
-      return;
+      if constexpr (sizeof(T) == 2) {
+        if (cs.KH * cs.KW * cs.Cin > fwd_db_maxk())
+          return launch(stats ? k_conv_fwd_sb<true> : k_conv_fwd_sb<false>,
+                        grid, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
+      }
+      return launch(stats ? k_conv_fwd_db<T, true> : k_conv_fwd_db<T, false>,
+                    grid, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
     }
-    bool g = p2 && cs.Cin % 4 == 0 && (((uintptr_t)x & 15) == 0);
-    auto kern = g ? k_conv_fwd<float, true, true>
-                  : (p2 ? k_conv_fwd<float, true, false>
-                        : k_conv_fwd<float, false, false>);
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s,
-                       (const float*)x, (const float*)w, (const float*)bias,
-                       (const float*)nullptr, (float*)y, (const float*)zero16,
-                       cs, act);
-  } else {
-    if (w_t2 && cs.KH * cs.KW * cs.Cin > fwd_db_maxk()) {
-      auto kern = stats ? k_conv_fwd_sb<true> : k_conv_fwd_sb<false>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const bf16*)x,
-                         (const bf16*)w_t2, (const bf16*)bias, (bf16*)y,
-                         (const bf16*)zero16, cs, act, stats);
-      return;
-    }
-    if (w_t2) {
-      auto kern = stats ? k_conv_fwd_db<bf16, true, true>
-                        : k_conv_fwd_db<bf16, true>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const bf16*)x,
-                         (const bf16*)w_t2, (const float*)nullptr,
-                         (const bf16*)bias, (bf16*)y, (const bf16*)zero16, cs,
-                         act, stats);
-      return;
-    }
-    bool g = p2 && cs.Cin % 8 == 0 && (((uintptr_t)x & 15) == 0);
-    auto kern = g ? k_conv_fwd<bf16, true, true>
-                  : (p2 ? k_conv_fwd<bf16, true, false>
-                        : k_conv_fwd<bf16, false, false>);
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s,
-                       (const bf16*)x, (const bf16*)w, (const float*)nullptr,
-                       (const bf16*)bias, (bf16*)y, (const bf16*)zero16, cs,
-                       act);
-  }
+    launch(g ? k_conv_fwd<T, true, true>
+             : (p2 ? k_conv_fwd<T, true, false> : k_conv_fwd<T, false, false>),
+           grid, s, X, (const T*)w, B, Y, Z, cs, act);
+  });
 }
 
 bool conv2d_dgrad_wants_db(DT dt, const void* dy, const ConvShape& cs) {
-  static const bool db_on = []() {
-    const char* e = getenv("TNN_FWD_DB");
-    return !(e && atoi(e) == 0);
-  }();
-  if (!db_on) return false;
-  static const int maxk = []() {
-    const char* e = getenv("TNN_DB_MAXK_DGRAD");
-    return e ? atoi(e) : 4608;  // dgrad ties-or-wins with DB up to here
-  }();
-  int v = dt == DT::F32 ? 4 : 8;
+  if (!db_on()) return false;
+  // dgrad ties-or-wins with the double buffer up to here
+  static const int maxk = env_int("TNN_DB_MAXK_DGRAD", 4608);
   return cs.KH * cs.KW * cs.Cout <= maxk && all_pow2(cs) &&
-         cs.Cout % v == 0 && (((uintptr_t)dy & 15) == 0);
+         vec_ok(dt, dy, cs.Cout);
 }
 
-void transpose_w_dgrad_launch(DT dt, const void* w, void* w_t2d, int KHW,
-                              int Cin, int Cout, hipStream_t s) {
-  int V = dt == DT::F32 ? 4 : 8;
-  if (Cout % V == 0 && (((uintptr_t)w & 15) == 0)) {
-    int64_t n = (int64_t)KHW * Cin * (Cout / V);
-    int blocks = (int)((n + 255) / 256);
-    if (dt == DT::F32)
-      hipLaunchKernelGGL(k_transpose_w_dgrad_vec<float>, dim3(blocks),
-                         dim3(256), 0, s, (const float*)w, (float*)w_t2d, KHW,
-                         Cin, Cout);
-    else
-      hipLaunchKernelGGL(k_transpose_w_dgrad_vec<bf16>, dim3(blocks),
-                         dim3(256), 0, s, (const bf16*)w, (bf16*)w_t2d, KHW,
-                         Cin, Cout);
-    return;
-  }
-  int64_t n = (int64_t)KHW * Cin * Cout;
-  int blocks = (int)((n + 255) / 256);
-  if (dt == DT::F32)
-    hipLaunchKernelGGL(k_transpose_w_dgrad<float>, dim3(blocks), dim3(256), 0,
-                       s, (const float*)w, (float*)w_t2d, KHW, Cin, Cout);
-  else
-    hipLaunchKernelGGL(k_transpose_w_dgrad<bf16>, dim3(blocks), dim3(256), 0,
-                       s, (const bf16*)w, (bf16*)w_t2d, KHW, Cin, Cout);
-}
-
+// Route, first match (w_t2d is passed iff conv2d_dgrad_wants_db: switch on,
+// all-pow2, vector gate, KH*KW*Cout <= TNN_DB_MAXK_DGRAD; else w_t).
+// parity = all-pow2, stride 2x2, even H and W, pow2 per-class divisors: 4
+// classes in grid.z over an M/4-row problem (see DgradClass), cs with the
+// per-class divisors.
+//   w_t2d, parity                 k_conv_dgrad_db<T, S2>
+//   w_t2d, stride 1x1             k_conv_dgrad_db<T, -, S1>
+//   w_t2d                         k_conv_dgrad_db<T>           (any stride)
+//   vector gate, parity           k_conv_dgrad<T, true, true, S2>
+//   vector gate, stride 1x1       k_conv_dgrad<T, true, true, -, S1>
+//   vector gate                   k_conv_dgrad<T, true, true>
+//   all-pow2                      k_conv_dgrad<T, true, false>
+//   otherwise                     k_conv_dgrad<T, false, false>
 void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
                          const void* w_t2d, void* dx, const void* zero16,
                          const ConvShape& cs, hipStream_t s) {
   int M = cs.N * cs.H * cs.W;
   dim3 grid(ceil_div(M, BM), ceil_div(cs.Cin, BN));
   bool p2 = all_pow2(cs);
-  // stride-2 parity decomposition (see k_conv_dgrad<..., S2>): 4 classes in
-  // grid.z over an M/4-row problem with only the stride-compatible (kh,kw)
-  // taps in K. Requires even spatial dims; routed through the glds variant.
+  bool g = p2 && vec_ok(dt, dy, cs.Cout);
+  bool s1 = cs.SH == 1 && cs.SW == 1;
   bool s2 = p2 && cs.SH == 2 && cs.SW == 2 && cs.H % 2 == 0 && cs.W % 2 == 0;
   ConvShape cs2 = cs;
   if (s2) {
@@ -1391,73 +1278,29 @@ void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
   }
   dim3 grid_s2(ceil_div(cs.N * (cs.H / 2) * (cs.W / 2), BM),
                ceil_div(cs.Cin, BN), 4);
-  if (dt == DT::F32) {
-    bool g = p2 && cs.Cout % 4 == 0 && (((uintptr_t)dy & 15) == 0);
-    if (w_t2d && s2) {
-      hipLaunchKernelGGL((k_conv_dgrad_db<float, true, true>), grid_s2,
-                         dim3(THREADS), 0, s, (const float*)dy,
-                         (const float*)w_t2d, (float*)dx, (const float*)zero16,
-                         cs2);
-      return;
-    }
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto DY = (const T*)dy;
+    auto DX = (T*)dx;
+    auto Z = (const T*)zero16;
     if (w_t2d) {
-      auto kern = cs.SH == 1 && cs.SW == 1
-                      ? k_conv_dgrad_db<float, true, false, true>
-                      : k_conv_dgrad_db<float, true>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const float*)dy,
-                         (const float*)w_t2d, (float*)dx,
-                         (const float*)zero16, cs);
-      return;
+      auto WT = (const T*)w_t2d;
+      if (s2)
+        return launch(k_conv_dgrad_db<T, true>, grid_s2, s, DY, WT, DX, Z,
+                      cs2);
+      return launch(s1 ? k_conv_dgrad_db<T, false, true> : k_conv_dgrad_db<T>,
+                    grid, s, DY, WT, DX, Z, cs);
     }
-    if (g && s2) {
-      hipLaunchKernelGGL((k_conv_dgrad<float, true, true, true>), grid_s2,
-                         dim3(THREADS), 0, s, (const float*)dy,
-                         (const float*)w_t, (float*)dx, (const float*)zero16,
-                         cs2);
-      return;
-    }
-    bool s1 = cs.SH == 1 && cs.SW == 1;
-    auto kern = g ? (s1 ? k_conv_dgrad<float, true, true, false, true>
-                        : k_conv_dgrad<float, true, true>)
-                  : (p2 ? k_conv_dgrad<float, true, false>
-                        : k_conv_dgrad<float, false, false>);
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s,
-                       (const float*)dy, (const float*)w_t, (float*)dx,
-                       (const float*)zero16, cs);
-  } else {
-    bool g = p2 && cs.Cout % 8 == 0 && (((uintptr_t)dy & 15) == 0);
-    if (w_t2d && s2) {
-      hipLaunchKernelGGL((k_conv_dgrad_db<bf16, true, true>), grid_s2,
-                         dim3(THREADS), 0, s, (const bf16*)dy,
-                         (const bf16*)w_t2d, (bf16*)dx, (const bf16*)zero16,
-                         cs2);
-      return;
-    }
-    if (w_t2d) {
-      auto kern = cs.SH == 1 && cs.SW == 1
-                      ? k_conv_dgrad_db<bf16, true, false, true>
-                      : k_conv_dgrad_db<bf16, true>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const bf16*)dy,
-                         (const bf16*)w_t2d, (bf16*)dx, (const bf16*)zero16,
-                         cs);
-      return;
-    }
-    if (g && s2) {
-      hipLaunchKernelGGL((k_conv_dgrad<bf16, true, true, true>), grid_s2,
-                         dim3(THREADS), 0, s, (const bf16*)dy,
-                         (const bf16*)w_t, (bf16*)dx, (const bf16*)zero16,
-                         cs2);
-      return;
-    }
-    bool s1 = cs.SH == 1 && cs.SW == 1;
-    auto kern = g ? (s1 ? k_conv_dgrad<bf16, true, true, false, true>
-                        : k_conv_dgrad<bf16, true, true>)
-                  : (p2 ? k_conv_dgrad<bf16, true, false>
-                        : k_conv_dgrad<bf16, false, false>);
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s,
-                       (const bf16*)dy, (const bf16*)w_t, (bf16*)dx,
-                       (const bf16*)zero16, cs);
-  }
+    auto WT = (const T*)w_t;
+    if (g && s2)
+      return launch(k_conv_dgrad<T, true, true, true>, grid_s2, s, DY, WT, DX,
+                    Z, cs2);
+    launch(g ? (s1 ? k_conv_dgrad<T, true, true, false, true>
+                   : k_conv_dgrad<T, true, true>)
+             : (p2 ? k_conv_dgrad<T, true, false>
+                   : k_conv_dgrad<T, false, false>),
+           grid, s, DY, WT, DX, Z, cs);
+  });
 }
 
 int conv2d_wgrad_zsplits(const ConvShape& cs) {
@@ -1470,6 +1313,13 @@ int conv2d_wgrad_zsplits(const ConvShape& cs) {
   return std::max(z, 1);
 }
 
+// Route, first match (vector gate: all-pow2, Cin and Cout multiples of the
+// vector width, x and dy 16-byte aligned):
+//   vector gate, bf16             k_conv_wgrad_tr
+//   vector gate, fp32             k_conv_wgrad_vec<float>
+//   all-pow2                      k_conv_wgrad<T, true>
+//   otherwise                     k_conv_wgrad<T, false>
+// then the split-M reduce unless the kernel wrote dw_out directly.
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
                          const ConvShape& cs, bool bias, hipStream_t s) {
@@ -1483,42 +1333,22 @@ void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
   float* target = direct ? (float*)dw_out : ws;
   dim3 grid(ceil_div(Kout, BM), ceil_div(cs.Cout, BN), z);
   bool p2 = all_pow2(cs);
-  if (dt == DT::F32) {
-    bool vec = p2 && cs.Cin % 4 == 0 && cs.Cout % 4 == 0 &&
-               (((uintptr_t)x & 15) == 0) && (((uintptr_t)dy & 15) == 0);
+  bool vec = p2 && vec_ok(dt, x, cs.Cin) && vec_ok(dt, dy, cs.Cout);
+  dispatch_dt(dt, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto X = (const T*)x;
+    auto DY = (const T*)dy;
+    auto Z = (const T*)zero16;
     if (vec) {
-      hipLaunchKernelGGL((k_conv_wgrad_vec<float, true>), grid, dim3(THREADS),
-                         0, s, (const float*)x, (const float*)dy, target,
-                         (const float*)zero16, cs, bias_row);
-    } else {
-      auto kern = p2 ? k_conv_wgrad<float, true> : k_conv_wgrad<float, false>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const float*)x,
-                         (const float*)dy, target, cs, bias_row);
+      if constexpr (sizeof(T) == 2)
+        launch(k_conv_wgrad_tr, grid, s, X, DY, target, Z, cs, bias_row);
+      else
+        launch(k_conv_wgrad_vec<T>, grid, s, X, DY, target, Z, cs, bias_row);
+      return;
     }
-  } else {
-    bool vec = p2 && cs.Cin % 8 == 0 && cs.Cout % 8 == 0 &&
-               (((uintptr_t)x & 15) == 0) && (((uintptr_t)dy & 15) == 0);
-    // TNN_WGRAD_TR=0 (read once) routes bf16 back to the register-staged
-    // kernel, so both paths can be compared from one build
-    static const bool tr_on = []() {
-      const char* e = getenv("TNN_WGRAD_TR");
-      return !(e && atoi(e) == 0);
-    }();
-    if (vec && tr_on) {
-      hipLaunchKernelGGL(k_conv_wgrad_tr, grid, dim3(THREADS), 0, s,
-                         (const bf16*)x,
-                         (const bf16*)dy, target, (const bf16*)zero16, cs,
-                         bias_row);
-    } else if (vec) {
-      hipLaunchKernelGGL((k_conv_wgrad_vec<bf16, true>), grid, dim3(THREADS),
-                         0, s, (const bf16*)x, (const bf16*)dy, target,
-                         (const bf16*)zero16, cs, bias_row);
-    } else {
-      auto kern = p2 ? k_conv_wgrad<bf16, true> : k_conv_wgrad<bf16, false>;
-      hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, (const bf16*)x,
-                         (const bf16*)dy, target, cs, bias_row);
-    }
-  }
+    launch(p2 ? k_conv_wgrad<T, true> : k_conv_wgrad<T, false>, grid, s, X,
+           DY, target, cs, bias_row);
+  });
   // the reduce kernel (and so dw's summation order) is chosen from dw's own
   // size: with Cout % 4 == 0 the extra row never changes dw's bits (else the
   // longer output can fall off the float4 reduce; still deterministic)
@@ -1526,18 +1356,6 @@ void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
     splitk_reduce_launch(ws, dw_out, out_dt, z,
                          (int64_t)(Kout + bias_row) * cs.Cout, s,
                          (int64_t)Kout * cs.Cout);
-}
-
-void transpose_w_launch(DT dt, const void* w, void* w_t, int KH, int KW,
-                        int Cin, int Cout, hipStream_t s) {
-  // batched [Cin, Cout] -> [Cout, Cin] transpose per (kh,kw) slice
-  dim3 grid((Cout + 31) / 32, (Cin + 31) / 32, KH * KW);
-  if (dt == DT::F32)
-    hipLaunchKernelGGL(k_transpose2d_tiled<float>, grid, dim3(256), 0, s,
-                       (const float*)w, (float*)w_t, Cin, Cout);
-  else
-    hipLaunchKernelGGL(k_transpose2d_tiled<bf16>, grid, dim3(256), 0, s,
-                       (const bf16*)w, (bf16*)w_t, Cin, Cout);
 }
 
 }  // namespace tnn

@@ -39,23 +39,6 @@ struct Epilogue {
   }
 };
 
-// 16 bytes of row_base[idx .. idx+V): one vector load when the span is
-// inside [0, limit) and 16B-aligned, else element-wise with zero fill.
-template <typename T>
-DEV Pack16<T> load16_guarded(const T* row_base, int idx, int limit) {
-  constexpr int V = 16 / sizeof(T);
-  const T* src = row_base + idx;
-  Pack16<T> v = {};
-  if (idx + V <= limit && aligned16(src)) {
-    v = *(const Pack16<T>*)src;
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j)
-      if (idx + j < limit) v.e[j] = src[j];
-  }
-  return v;
-}
-
 // Stage ROWS k-contiguous rows src[row0 + r][k0 .. k0 + BK) (row stride K)
 // as the swizzled LDS image dst[r][k]; rows >= nrows and k >= K are zero.
 template <typename T, int ROWS>
@@ -170,20 +153,6 @@ DEV void nt_db_mainloop(const T* __restrict__ A, const T* __restrict__ B,
     __builtin_amdgcn_s_barrier();
   }
 }
-
-// host side: DT -> element type. f receives a TypeTag<float> or
-// TypeTag<bf16>, so each launcher body is written once:
-//   dispatch_dt(dt, [&](auto tag) {
-//     using T = typename decltype(tag)::type; ... });
-template <typename T> struct TypeTag { using type = T; };
-template <typename F>
-static void dispatch_dt(DT dt, F&& f) {
-  if (dt == DT::F32) f(TypeTag<float>{});
-  else f(TypeTag<bf16>{});
-}
-
-// elements per 16-byte vector; glds / vector routes need K % this == 0
-static int vec_elems(DT dt) { return dt == DT::F32 ? 4 : 8; }
 
 // ---------------------------------------------------------------------------
 // NN / NT kernel: C[M,N] = act(A[M,K] @ B + bias) + resid

@@ -3,6 +3,9 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#ifdef __HIPCC__  // the bindings go through the host compiler, which cannot
+#include <hip/hip_bf16.h>  // parse this header
+#endif
 #include <algorithm>
 #include <cstdint>
 
@@ -12,6 +15,22 @@ enum class DT { F32, BF16 };
 
 // host-side check that a device pointer can take 16-byte vector access
 inline bool ptr_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// elements per 16-byte vector; glds / vector routes need K % this == 0
+inline int vec_elems(DT dt) { return dt == DT::F32 ? 4 : 8; }
+
+#ifdef __HIPCC__
+// launchers: DT -> element type. f receives a TypeTag<float> or
+// TypeTag<bf16>, so each launcher body is written once:
+//   dispatch_dt(dt, [&](auto tag) {
+//     using T = typename decltype(tag)::type; ... });
+template <typename T> struct TypeTag { using type = T; };
+template <typename F>
+inline void dispatch_dt(DT dt, F&& f) {
+  if (dt == DT::F32) f(TypeTag<float>{});
+  else f(TypeTag<__hip_bfloat16>{});
+}
+#endif
 
 // ---- elementwise.hip -------------------------------------------------------
 void act_fwd_launch(DT dt, const void* x, void* y, int64_t n, int kind,

@@ -41,6 +41,23 @@ DEV bool aligned16(const T* p) {
   return ((unsigned long long)(const void*)p & 15ull) == 0;
 }
 
+// 16 bytes of row_base[idx .. idx+V): one vector load when the span is
+// inside [0, limit) and 16B-aligned, else element-wise with zero fill.
+template <typename T>
+DEV Pack16<T> load16_guarded(const T* row_base, int idx, int limit) {
+  constexpr int V = 16 / sizeof(T);
+  const T* src = row_base + idx;
+  Pack16<T> v = {};
+  if (idx + V <= limit && aligned16(src)) {
+    v = *(const Pack16<T>*)src;
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      if (idx + j < limit) v.e[j] = src[j];
+  }
+  return v;
+}
+
 // element offset of tile element (row, col) in the swizzled [rows][BK]
 // image; the XOR only touches byte bits 4-6, so any 16B-aligned col keeps
 // its vector contiguous and the swizzle stays inside the row.
