@@ -2,8 +2,14 @@
 asymmetric random operands — cdna guide §5.4 rules 16/25)."""
 
 
+import os
+import sys
+
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import attn_oracle as A  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +33,26 @@ def ref_attention(q, k, v, causal):
 
 def maxerr(a, b):
     return (a.float() - b.float()).abs().max().item()
+
+
+def assert_vs_float64(tag, q, k, v, do, causal, got):
+    """got {kind: kernel output} against float64, by attn_oracle's relative
+    metric and bounds (test_gpu_attention_oracle.py is the full grid). The
+    CPU rounding model of the same inputs is held to the same bounds, which
+    shows that the inputs allow them: at S=128 with unit normals it sits at
+    or below a third of each bound. Not used on this file's long causal
+    cases: with a flat softmax rms(o) shrinks with S while row 0 still
+    equals v[0], and the model itself comes within 20% of the o and dv
+    bounds at S=1000."""
+    q, k, v, do = (t.detach().cpu() for t in (q, k, v, do))
+    ref = A.ref64_grads(q, k, v, do, causal)
+    model = A.errors(A.emulate(q, k, v, do, causal), ref)
+    err = A.errors(got, ref)
+    print(tag, {kd: f"kernel {err[kd]:.3e} model {model[kd]:.3e} "
+                    f"bound {A.BOUND[kd]:.3e}" for kd in err})
+    for kd in err:
+        assert model[kd] <= A.BOUND[kd], (tag, kd, model[kd])
+        assert err[kd] <= A.BOUND[kd], (tag, kd, err[kd])
 
 
 @pytest.mark.parametrize("causal", [False, True])
@@ -98,6 +124,8 @@ def test_flash_autograd_function():
     o = flash_attention(q, k, v, causal=True)
     o.sum().backward()
     assert q.grad is not None and torch.isfinite(q.grad.float()).all()
+    assert_vs_float64("flash_attention", q, k, v, torch.ones_like(q), True,
+                      {"o": o, "dq": q.grad, "dk": k.grad, "dv": v.grad})
 
 
 def test_gpt_block_gpu():

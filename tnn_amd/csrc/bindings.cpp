@@ -929,13 +929,35 @@ static std::array<int64_t, 3> attn_strides(const at::Tensor& t) {
   return {t.stride(2), t.stride(1), t.stride(0)};
 }
 
+// the kernels take one {B,H,S,D} and one stride tuple for q, k and v and
+// trust every other tensor to match them: check all of it before a launch
+static void attn_check_like(const char* fn, const char* name,
+                            const at::Tensor& t, const at::Tensor& q,
+                            at::IntArrayRef sizes, at::ScalarType dtype) {
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), fn, ": ", name,
+              " must be on q's GPU (", q.device(), "), got ", t.device());
+  TORCH_CHECK(t.scalar_type() == dtype, fn, ": ", name, " must be ", dtype,
+              ", got ", t.scalar_type());
+  TORCH_CHECK(t.sizes() == sizes, fn, ": ", name, " must be ", sizes,
+              ", got ", t.sizes());
+}
+
+static void attn_check_qkv(const char* fn, const at::Tensor& q,
+                           const at::Tensor& k, const at::Tensor& v) {
+  TORCH_CHECK(q.is_cuda(), fn, ": q must be on GPU");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16, fn,
+              ": flash attention is bf16, got q ", q.scalar_type());
+  TORCH_CHECK(q.dim() == 4, fn, ": q must be [B,H,S,D]");
+  TORCH_CHECK(q.size(3) == 64 || q.size(3) == 128, fn,
+              ": head dim must be 64 or 128, got ", q.size(3));
+  attn_check_like(fn, "k", k, q, q.sizes(), at::kBFloat16);
+  attn_check_like(fn, "v", v, q, q.sizes(), at::kBFloat16);
+}
+
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  bool causal) {
-  TORCH_CHECK(q.is_cuda(), "q must be on GPU");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "flash attention is bf16");
-  TORCH_CHECK(q.dim() == 4, "q must be [B,H,S,D]");
+  attn_check_qkv("attn_fwd", q, k, v);
   int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128, got ", D);
   const bool strided_ok = attn_view_ok(q, true) && attn_view_ok(k, true) &&
                           attn_view_ok(v, true) &&
                           q.strides() == k.strides() &&
@@ -962,7 +984,13 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  c10::optional<at::Tensor> dq_out,
                                  c10::optional<at::Tensor> dk_out,
                                  c10::optional<at::Tensor> dv_out) {
-  TORCH_CHECK(q.is_cuda() && dout.is_cuda(), "attn_bwd wants GPU tensors");
+  attn_check_qkv("attn_bwd", q, k, v);
+  attn_check_like("attn_bwd", "o", o, q, q.sizes(), at::kBFloat16);
+  attn_check_like("attn_bwd", "dout", dout, q, q.sizes(), at::kBFloat16);
+  attn_check_like("attn_bwd", "lse", lse, q, q.sizes().slice(0, 3),
+                  at::kFloat);
+  // the kernels index lse as [bh * S + row]
+  TORCH_CHECK(lse.is_contiguous(), "attn_bwd: lse must be contiguous");
   int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const bool in_ok = attn_view_ok(q, true) && attn_view_ok(k, true) &&
                      attn_view_ok(v, true) && q.strides() == k.strides() &&
@@ -977,6 +1005,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
     // caller-provided grad views (e.g. three slices of one merged dQKV
     // buffer: the fused-QKV backward writes it in place, no cat/pad)
     dq = *dq_out; dk = *dk_out; dv = *dv_out;
+    attn_check_like("attn_bwd", "dq_out", dq, q, q.sizes(), at::kBFloat16);
+    attn_check_like("attn_bwd", "dk_out", dk, q, q.sizes(), at::kBFloat16);
+    attn_check_like("attn_bwd", "dv_out", dv, q, q.sizes(), at::kBFloat16);
     TORCH_CHECK(dq.strides() == dk.strides() && dk.strides() == dv.strides()
                     && dq.stride(3) == 1,
                 "grad views must share a d-contiguous stride tuple");
