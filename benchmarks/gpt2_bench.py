@@ -16,8 +16,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tnn_amd import models
 from tnn_amd.nn import CrossEntropyLoss, AdamW
 from tnn_amd.nn.layer import cast_compute_dtype
-from tnn_amd.models.generate import (generate, generate_batch,
-                                      generate_cached, generate_graphed)
+from tnn_amd.models.generate import (DecodeSession, generate,
+                                      generate_batch, generate_cached,
+                                      generate_graphed)
 
 
 def main():
@@ -30,6 +31,11 @@ def main():
     p.add_argument("--decode-batch", type=int, default=0,
                    help="also time generate_batch over this many ragged "
                         "prompts (greedy, one captured step for all rows)")
+    p.add_argument("--second-turn", action="store_true",
+                   help="time a second turn of 64 tokens onto 8 live "
+                        "contexts of 768 (DecodeSession) against "
+                        "generate_batch on the concatenated prompts; wants "
+                        "--seq-len 1024")
     p.add_argument("--train", action="store_true", default=True)
     p.add_argument("--graph", action="store_true",
                    help="also time the hipGraph-captured whole train step")
@@ -132,6 +138,56 @@ def main():
         print(f"decode [batched x{args.decode_batch}]: {n} tokens in "
               f"{dt:.2f}s = {n / dt:.2f} tok/s aggregate, "
               f"{n / dt / args.decode_batch:.2f} tok/s per sequence")
+    if args.second_turn:
+        second_turn(model, dev, args.seq_len, args.decode_tokens)
+
+
+def second_turn(model, dev, seq_len, n_tokens, rows=8, ctx_len=768, turn=64):
+    """Second user turn onto live contexts: DecodeSession.generate (extend
+    over the cached prefix) against generate_batch (close + full
+    re-prefill of context + turn). Time to first token is a call with
+    max_new_tokens=1. The routes alternate; the last of 3 rounds counts."""
+    g = torch.Generator().manual_seed(0)
+    ctx = [torch.randint(0, 50257, (ctx_len,), generator=g).tolist()
+           for _ in range(rows)]
+    new = [torch.randint(0, 50257, (turn,), generator=g).tolist()
+           for _ in range(rows)]
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+
+    def timed(fn):
+        sync()
+        t0 = time.perf_counter()
+        out = fn()
+        sync()
+        return time.perf_counter() - t0, out
+
+    sess = DecodeSession(model, rows, seq_len=seq_len, device=dev)
+    try:
+        sess.generate(ctx, max_new_tokens=0, eot_token=None)   # first turn
+        res = {}
+        for _ in range(3):
+            for n, tag in ((1, "first token"), (n_tokens, "total")):
+                sess.rewind([ctx_len] * rows)
+                res["session", tag] = timed(lambda: sess.generate(
+                    new, max_new_tokens=n, eot_token=None))
+                res["batch", tag] = timed(lambda: generate_batch(
+                    model, [c + t for c, t in zip(ctx, new)],
+                    max_new_tokens=n, seq_len=seq_len, device=dev,
+                    eot_token=None))
+                # generate_batch closed the model's caches: reopen and
+                # refill the session outside the timed region
+                sess.close()
+                sess = DecodeSession(model, rows, seq_len=seq_len, device=dev)
+                sess.generate(ctx, max_new_tokens=0, eot_token=None)
+        for tag in ("first token", "total"):
+            print(f"second turn [{rows} x {ctx_len}+{turn}, {n_tokens} new] "
+                  f"{tag}: DecodeSession {res['session', tag][0] * 1e3:.1f} ms"
+                  f" | generate_batch {res['batch', tag][0] * 1e3:.1f} ms")
+    finally:
+        sess.close()
 
 
 if __name__ == "__main__":

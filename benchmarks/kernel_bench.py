@@ -121,6 +121,43 @@ def bench_attn():
                2.5 * fl)
 
 
+def bench_attn_extend():
+    """Extend attention (T new rows per sequence at prefix pos) against the
+    cached-prefill route it replaces, sdpa_materialized over the live
+    prefix with qoff = pos, and -- at pos = 0, where the work is the same
+    -- causal attn_fwd at S = T. The routes of a shape are timed in turn,
+    twice; the better round is reported. FLOPs count visible keys only."""
+    from tnn_amd import ops
+    cap = 1024
+    for B, H, D in [(8, 12, 64), (8, 20, 64), (8, 8, 128)]:
+        kc = torch.randn(B, H, cap, D, dtype=torch.bfloat16, device=DEV)
+        vc = torch.randn_like(kc)
+        for pos, T in [(0, 128), (0, 512), (0, 1024), (512, 512), (960, 64),
+                       (1016, 8)]:
+            qkv = torch.randn(B, T, 3 * H * D, dtype=torch.bfloat16,
+                              device=DEV)
+            q = qkv[..., :H * D].view(B, T, H, D).transpose(1, 2)
+            pos_t = torch.full((B,), pos, dtype=torch.int64, device=DEV)
+            kl, vl = kc[:, :, :pos + T], vc[:, :, :pos + T]
+            routes = {
+                "attn_extend": lambda: ext.attn_extend(q, kc, vc, pos_t, None,
+                                                       D ** -0.5),
+                "sdpa_materialized": lambda: ops.sdpa_materialized(
+                    q, kl, vl, causal=True, qoff=pos)}
+            if pos == 0:
+                qd, kd, vd = q.contiguous(), kl.contiguous(), vl.contiguous()
+                routes["attn_fwd"] = lambda: ext.attn_fwd(qd, kd, vd, True)
+            fl = 4.0 * B * H * D * (T * pos + T * (T + 1) / 2)
+            best = {}
+            with torch.no_grad():
+                for _ in range(2):
+                    for name, fn in routes.items():
+                        secs = timeit(fn)
+                        best[name] = min(secs, best.get(name, secs))
+            for name, secs in best.items():
+                report(name, f"B{B} H{H} D{D} pos{pos} T{T}", secs, fl)
+
+
 def bench_bmm():
     # materialized-scores attention shapes (per-head batched QK^T)
     for BH, S, D in [(96, 512, 64), (32, 2048, 128)]:
@@ -255,7 +292,8 @@ def bench_gradnorm():
 
 ALL = {"gemm": bench_gemm, "conv": bench_conv, "bn": bench_bn,
        "colsum": bench_colsum, "ce": bench_ce, "attn": bench_attn,
-       "bmm": bench_bmm, "softmax": bench_softmax, "ln": bench_ln,
+       "attn_extend": bench_attn_extend, "bmm": bench_bmm,
+       "softmax": bench_softmax, "ln": bench_ln,
        "gn": bench_gn, "decode": bench_decode, "skinny": bench_skinny,
        "sample": bench_sample, "gradnorm": bench_gradnorm}
 

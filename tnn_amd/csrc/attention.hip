@@ -25,6 +25,11 @@
 // All transposed stagings use the same b64 transpose-pack; the dS
 // natural-image scatter packs 4 kv-contiguous values per ds_write_b64.
 //
+// Extend (k_attn_ext, inference): the forward structure for T new query
+// rows per sequence against that sequence's own KV-cache prefix, with the
+// prefix length and the row count read from device memory (see the
+// comment above the kernel).
+//
 // LDS images use the tile_gemm XOR swizzle (bank-conflict free for the
 // vector fragment reads and the b64 transpose writes).
 
@@ -382,6 +387,178 @@ __global__ void k_attn_fwd(const bf16* __restrict__ Q, const bf16* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// Extend attention (inference): T new query rows of sequence b against that
+// sequence's own KV-cache prefix, always causal with the prefix as offset.
+// Same structure as k_attn_fwd (Q fragments in registers, double-buffered
+// K via glds and V^T via the split load/write, denominator on the 17th PV
+// fragment); what differs:
+//   * q rows come through their own {row, head, batch} strides (the head
+//     slices of a merged [B,T,3*H*D] projection); K/V are the dense
+//     [B,H,cap,D] caches; o goes out through a third stride tuple;
+//   * the extent is read from device memory and clamped here, so a bad
+//     position can never take a read outside the cache:
+//       p0 = clamp(pos[b], 0, cap), n = clamp(n_new ? n_new[b] : T, 0,
+//       min(T, cap - p0)), kv_len = p0 + n; row i < n sees keys j <= p0 + i;
+//   * a block whose first row is >= n stores zeros and leaves before the
+//     first barrier (block-uniform: p0 and n depend on blockIdx alone);
+//   * rows i >= n of a partly live block are stored as zeros; their q
+//     rows are staged from the zero page, so nothing of them is read;
+//   * cache slots >= kv_len never enter the result: K rows from the zero
+//     page, V rows zeroed in TStage::load, scores masked -- a NaN in a
+//     dead slot cannot reach o;
+//   * no LSE.
+// The grid depends on (T, B, H) alone, so a launch is hipGraph-capturable
+// while pos / n_new change between replays.
+template <int D, int NW>
+__launch_bounds__(NW * 64)
+__global__ void k_attn_ext(const bf16* __restrict__ Q, const bf16* __restrict__ K,
+                           const bf16* __restrict__ V, bf16* __restrict__ O,
+                           const int64_t* __restrict__ pos,
+                           const int64_t* __restrict__ n_new,
+                           const bf16* __restrict__ zero16, int T, int cap,
+                           int H, int64_t q_rs, int64_t q_hs, int64_t q_bs,
+                           int64_t o_rs, int64_t o_hs, int64_t o_bs,
+                           float scale) {
+  constexpr int BQ = NW * 16;
+  constexpr int THREADS = NW * 64;
+  constexpr int FN = BKV / 16;
+  constexpr int FO = D / 16;
+  __shared__ alignas(16) bf16 q_lds[BQ * D];
+  __shared__ alignas(16) bf16 k_lds[2][BKV * D];
+  __shared__ alignas(16) bf16 vt_lds[2][(D + 16) * BKV];
+  bf16* p_lds = q_lds;  // aliased after the Q fragments are hoisted
+
+  const int q0 = blockIdx.x * BQ;
+  const int64_t bh = blockIdx.y;
+  const int64_t b = bh / H, h = bh % H;
+  const int p0 = (int)min(max(pos[b], (int64_t)0), (int64_t)cap);
+  const int n = (int)min(max(n_new ? n_new[b] : (int64_t)T, (int64_t)0),
+                         (int64_t)min(T, cap - p0));
+  const int kv_len = p0 + n;
+  bf16* o = O + b * o_bs + h * o_hs;
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wrow = wid * 16;
+  const int cr = (lane >> 4) * 4;
+  const int cc = lane & 15;
+
+  if (q0 >= n) {  // no live row in this block
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int grow = q0 + wrow + cr + j;
+      if (grow >= T) continue;
+#pragma unroll
+      for (int fo = 0; fo < FO; ++fo)
+        o[(int64_t)grow * o_rs + fo * 16 + cc] = f2bf(0.0f);
+    }
+    return;
+  }
+
+  const bf16* q = Q + b * q_bs + h * q_hs;
+  const bf16* k = K + bh * cap * D;
+  const bf16* v = V + bh * cap * D;
+
+  stage_tile<BQ, D, NW>(q + (int64_t)q0 * q_rs, q_lds, n - q0, zero16, q_rs);
+  for (int i = threadIdx.x; i < 16 * BKV; i += THREADS) {
+    const int rr = i / BKV, col = i % BKV;
+    const bf16 val = f2bf(rr == 0 ? 1.0f : 0.0f);
+    vt_lds[0][aoff<bf16, BKV>(D + rr, col)] = val;
+    vt_lds[1][aoff<bf16, BKV>(D + rr, col)] = val;
+  }
+  __syncthreads();
+  bf16x8 q_frag[D / 32];
+  {
+    const int r = lane & 15;
+#pragma unroll
+    for (int ks = 0; ks < D / 32; ++ks) {
+      const int kb = ks * 32 + (lane >> 4) * 8;
+      q_frag[ks] = *(const bf16x8*)&q_lds[aoff<bf16, D>(wrow + r, kb)];
+    }
+  }
+  __syncthreads();  // q_lds free -> p_lds
+
+  float m_run[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m_run[j] = -INFINITY;
+  f32x4 o_acc[FO + 1] = {};  // acc[FO] col 0 = running softmax denominator
+
+  // block-uniform trip count (p0, n, q0 are): the barriers below stay legal
+  const int kv_end = min(kv_len, p0 + q0 + BQ);
+  const int ntiles = (kv_end + BKV - 1) / BKV;
+  TStage<BKV, D, THREADS> vst;
+
+  stage_tile<BKV, D, NW>(k, k_lds[0], kv_len, zero16);
+  vst.load(v, kv_len);
+  vst.write(vt_lds[0]);
+  __syncthreads();
+
+  for (int t = 0; t < ntiles; ++t) {
+    const int cur = t & 1;
+    const int kv0 = t * BKV;
+    if (t + 1 < ntiles) {
+      stage_tile<BKV, D, NW>(k + (int64_t)(kv0 + BKV) * D, k_lds[cur ^ 1],
+                             kv_len - kv0 - BKV, zero16);
+      vst.load(v + (int64_t)(kv0 + BKV) * D, kv_len - kv0 - BKV);
+    }
+
+    f32x4 s_acc[FN] = {};
+    mma_nt_areg<D, FN>(q_frag, k_lds[cur], lane, s_acc);
+
+    float alpha[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int last = p0 + q0 + wrow + cr + j;  // newest key this row sees
+      float mx = -INFINITY;
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn) {
+        int gcol = kv0 + fn * 16 + cc;
+        float sv = s_acc[fn][j] * scale;
+        if (gcol >= kv_len || gcol > last) sv = -INFINITY;
+        s_acc[fn][j] = sv;
+        mx = fmaxf(mx, sv);
+      }
+      mx = row_reduce_max(mx);
+      float m_new = fmaxf(m_run[j], mx);
+      // all-masked row in this tile (last < kv0): keep everything unchanged
+      float a = (m_new == -INFINITY) ? 1.0f : __expf(m_run[j] - m_new);
+      if (m_run[j] == -INFINITY) a = 0.0f;
+      if (m_new == -INFINITY) a = 1.0f;
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn) {
+        float p = (s_acc[fn][j] == -INFINITY) ? 0.0f
+                                              : __expf(s_acc[fn][j] - m_new);
+        s_acc[fn][j] = p;
+      }
+      m_run[j] = m_new;
+      alpha[j] = a;
+    }
+    frag_to_lds<FN>(s_acc, p_lds + wid * 16 * BKV, lane);
+#pragma unroll
+    for (int fo = 0; fo <= FO; ++fo)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o_acc[fo][j] *= alpha[j];
+    mma_pv<FO + 1>(p_lds + wid * 16 * BKV, vt_lds[cur], 0, lane, o_acc);
+
+    if (t + 1 < ntiles)
+      vst.write(vt_lds[cur ^ 1]);
+    __syncthreads();
+  }
+
+  // epilogue: O = O / l for rows < n, zeros for rows in [n, T)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float l = __shfl(o_acc[FO][j], lane & 48, 64);
+    const int grow = q0 + wrow + cr + j;
+    if (grow >= T) continue;
+    float inv_l = (grow < n && l > 0.0f) ? 1.0f / l : 0.0f;
+#pragma unroll
+    for (int fo = 0; fo < FO; ++fo)
+      o[(int64_t)grow * o_rs + fo * 16 + cc] =
+          f2bf(grow < n ? o_acc[fo][j] * inv_l : 0.0f);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Di = rowsum(dO * O) per (b,h,row)
 __global__ void k_attn_dot(const bf16* __restrict__ dO,
                            const bf16* __restrict__ O, float* __restrict__ Di,
@@ -616,6 +793,41 @@ void attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
   } while (0)
   if (D == 64) { if (causal) PICK(64, true); else PICK(64, false); }
   else if (D == 128) { if (causal) PICK(128, true); else PICK(128, false); }
+#undef PICK
+#undef LAUNCH
+}
+
+// Extend attention: waves per block from the chunk length T, so a 3-token
+// turn or an 8-token draft does not pay for a 128-row q tile. Each block
+// restages every KV tile it visits, so wider blocks only pay off once the
+// chunk fills them:
+//
+//     T          NW   q rows / block   threads
+//     1 .. 16     1         16            64
+//     17 .. 64    4         64           256
+//     65 ..       8        128           512
+//
+// The grid, (ceil(T / (16 NW)), B*H), is fixed by shapes alone.
+void attn_ext_launch(const void* q, const void* k, const void* v, void* o,
+                     const int64_t* pos, const int64_t* n_new,
+                     const void* zero16, int B, int H, int T, int cap, int D,
+                     const int64_t* q_str, const int64_t* o_str, float scale,
+                     hipStream_t s) {
+#define LAUNCH(DD, NWV)                                                      \
+  hipLaunchKernelGGL((k_attn_ext<DD, NWV>),                                  \
+                     dim3((T + NWV * 16 - 1) / (NWV * 16), B * H),           \
+                     dim3(NWV * 64), 0, s, (const bf16*)q, (const bf16*)k,   \
+                     (const bf16*)v, (bf16*)o, pos, n_new,                   \
+                     (const bf16*)zero16, T, cap, H, q_str[0], q_str[1],     \
+                     q_str[2], o_str[0], o_str[1], o_str[2], scale)
+#define PICK(DD)                                                             \
+  do {                                                                       \
+    if (T <= 16) LAUNCH(DD, 1);                                              \
+    else if (T <= 64) LAUNCH(DD, 4);                                         \
+    else LAUNCH(DD, 8);                                                      \
+  } while (0)
+  if (D == 64) PICK(64);
+  else if (D == 128) PICK(128);
 #undef PICK
 #undef LAUNCH
 }

@@ -1295,6 +1295,118 @@ void kv_append(at::Tensor& k_cache, at::Tensor& v_cache,
                    v_new.stride(1), cur_stream());
 }
 
+// ---- extend attention / multi-row KV append --------------------------------
+// Shared checks: caches are matching contiguous [B,H,cap,D] on the GPU;
+// pos / n_new are contiguous device int64 [B]; 1 <= T <= cap.
+static void ext_check_caches(const char* fn, const at::Tensor& kc,
+                             const at::Tensor& vc) {
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() && kc.device() == vc.device(), fn,
+              ": caches must be on one GPU");
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() &&
+              vc.scalar_type() == kc.scalar_type() && kc.is_contiguous() &&
+              vc.is_contiguous(), fn,
+              ": caches must be matching contiguous [B,H,cap,D]");
+  TORCH_CHECK(kc.size(0) * kc.size(1) <= 65535, fn, ": B*H exceeds the grid");
+}
+
+static void ext_check_index(const char* fn, const char* name,
+                            const at::Tensor& t, const at::Tensor& kc) {
+  TORCH_CHECK(t.is_cuda() && t.device() == kc.device() &&
+              t.scalar_type() == at::kLong && t.dim() == 1 &&
+              t.numel() == kc.size(0) && t.is_contiguous(), fn, ": ", name,
+              " must be contiguous int64 [B] on the caches' GPU");
+}
+
+static void ext_check_rows(const char* fn, const char* name,
+                           const at::Tensor& t, const at::Tensor& kc) {
+  TORCH_CHECK(t.is_cuda() && t.device() == kc.device(), fn, ": ", name,
+              " must be on the caches' GPU");
+  TORCH_CHECK(t.scalar_type() == kc.scalar_type(), fn, ": ", name,
+              " must be ", kc.scalar_type(), ", got ", t.scalar_type());
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == kc.size(0) &&
+              t.size(1) == kc.size(1) && t.size(3) == kc.size(3), fn, ": ",
+              name, " must be [B,H,T,D] with the caches' B, H, D, got ",
+              t.sizes());
+  TORCH_CHECK(t.stride(3) == 1, fn, ": ", name,
+              " must have unit stride along D");
+  TORCH_CHECK(t.size(2) >= 1 && t.size(2) <= kc.size(2), fn,
+              ": T must be in [1, cap], got ", t.size(2));
+}
+
+// q [B,H,T,D] bf16 view (unit d-stride, 16-byte aligned rows: the head
+// slices of a merged [B,T,3*H*D] projection qualify) against the dense
+// caches. Sequence b attends rows i < n_new[b] (all T when absent) at
+// positions pos[b] + i over keys [0, pos[b] + i]; rows >= n_new[b] come
+// back zero. o is [B,H,T,D] over [B,T,H,D] memory: o.transpose(1, 2) is
+// contiguous.
+at::Tensor attn_extend(const at::Tensor& q, const at::Tensor& k_cache,
+                       const at::Tensor& v_cache, const at::Tensor& pos,
+                       const c10::optional<at::Tensor>& n_new, double scale) {
+  const char* fn = "attn_extend";
+  ext_check_caches(fn, k_cache, v_cache);
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16, fn,
+              ": bf16 only, got ", k_cache.scalar_type());
+  const int64_t B = k_cache.size(0), H = k_cache.size(1),
+                cap = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(D == 64 || D == 128, fn, ": head dim must be 64 or 128, got ",
+              D);
+  ext_check_rows(fn, "q", q, k_cache);
+  TORCH_CHECK(attn_view_ok(q, true), fn,
+              ": q rows must be 16-byte aligned across t, h and the base");
+  ext_check_index(fn, "pos", pos, k_cache);
+  if (n_new.has_value()) ext_check_index(fn, "n_new", *n_new, k_cache);
+  const int64_t T = q.size(2);
+  auto o_buf = at::empty({B, T, H * D}, q.options());
+  auto o = o_buf.view({B, T, H, D}).permute({0, 2, 1, 3});
+  attn_ext_launch(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                  o_buf.data_ptr(), pos.data_ptr<int64_t>(),
+                  n_new.has_value() ? n_new->data_ptr<int64_t>() : nullptr,
+                  zero_page(q), (int)B, (int)H, (int)T, (int)cap, (int)D,
+                  attn_strides(q).data(), attn_strides(o).data(),
+                  (float)scale, cur_stream());
+  return o;
+}
+
+// k_new / v_new [B,H,T,D] views with unit d-stride (fp32 or bf16, the
+// caches' dtype): rows i < n_new[b] go to cache slot pos[b] + i; slots
+// >= cap and rows of a negative pos[b] are dropped.
+void kv_append_n(at::Tensor& k_cache, at::Tensor& v_cache,
+                 const at::Tensor& k_new, const at::Tensor& v_new,
+                 const at::Tensor& pos,
+                 const c10::optional<at::Tensor>& n_new) {
+  const char* fn = "kv_append_n";
+  ext_check_caches(fn, k_cache, v_cache);
+  const auto dt = dt_of(k_cache);
+  ext_check_rows(fn, "k_new", k_new, k_cache);
+  ext_check_rows(fn, "v_new", v_new, k_cache);
+  TORCH_CHECK(k_new.size(2) == v_new.size(2), fn,
+              ": k_new and v_new disagree on T");
+  ext_check_index(fn, "pos", pos, k_cache);
+  if (n_new.has_value()) ext_check_index(fn, "n_new", *n_new, k_cache);
+  const int64_t B = k_cache.size(0), H = k_cache.size(1),
+                cap = k_cache.size(2), D = k_cache.size(3);
+  const int64_t T = k_new.size(2);
+  // 16-byte vectors need every row start aligned: bases, all three
+  // strides and the row size
+  const int64_t per = 16 / k_cache.element_size();
+  auto vec_ok = [&](const at::Tensor& t) {
+    return ((uintptr_t)t.data_ptr() & 15) == 0 && t.stride(0) % per == 0 &&
+           t.stride(1) % per == 0 && t.stride(2) % per == 0;
+  };
+  const bool vec = D % per == 0 && vec_ok(k_new) && vec_ok(v_new) &&
+                   vec_ok(k_cache) && vec_ok(v_cache);
+  const std::array<int64_t, 3> ks = {k_new.stride(0), k_new.stride(1),
+                                     k_new.stride(2)};
+  const std::array<int64_t, 3> vs = {v_new.stride(0), v_new.stride(1),
+                                     v_new.stride(2)};
+  kv_append_n_launch(dt, k_cache.data_ptr(), v_cache.data_ptr(),
+                     k_new.data_ptr(), v_new.data_ptr(),
+                     pos.data_ptr<int64_t>(),
+                     n_new.has_value() ? n_new->data_ptr<int64_t>() : nullptr,
+                     (int)B, (int)H, (int)T, (int)cap, (int)D, ks.data(),
+                     vs.data(), vec, cur_stream());
+}
+
 // ---- on-device sampling ----------------------------------------------------
 // logits [R,V] bf16 -> ids [R] int64; step is a device int64 [1] (Philox
 // counter, advanced in-graph by the caller); u [R] fp32 overrides the RNG.
@@ -1399,6 +1511,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("smax_bwd", &tnn::smax_bwd);
   m.def("attn_decode", &tnn::attn_decode);
   m.def("kv_append", &tnn::kv_append);
+  m.def("attn_extend", &tnn::attn_extend);
+  m.def("kv_append_n", &tnn::kv_append_n);
   m.def("sample_logits", &tnn::sample_logits, py::arg("logits"),
         py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("step"), py::arg("u") = c10::nullopt);

@@ -192,4 +192,59 @@ void kv_append_launch(DT dt, void* kc, void* vc, const void* kn,
                        pos, H, cap, D, k_sb, k_sh, v_sb, v_sh);
 }
 
+// Multi-row KV append: sequence b's new K/V rows i < n_new[b] (all T when
+// n_new is absent) land at cache slot pos[b] + i. Rows that would land at
+// >= cap and every row of a negative pos[b] are dropped, so no position
+// can make the kernel write outside its sequence's cache. Sources are the
+// strided [B,H,T,D] views of the merged projection ({batch, head, row}
+// element strides, unit stride along D). One 64-lane block per (row, b*h);
+// `vec` (host-checked: 16-byte aligned bases, strides and row size) copies
+// 16-byte vectors, else element-wise.
+template <typename T>
+__launch_bounds__(64)
+__global__ void k_kv_append_n(T* __restrict__ kc, T* __restrict__ vc,
+                              const T* __restrict__ kn,
+                              const T* __restrict__ vn,
+                              const int64_t* __restrict__ pos,
+                              const int64_t* __restrict__ n_new, int Tn, int H,
+                              int cap, int D, int64_t k_sb, int64_t k_sh,
+                              int64_t k_sr, int64_t v_sb, int64_t v_sh,
+                              int64_t v_sr, bool vec) {
+  const int i = blockIdx.x;
+  const int b = blockIdx.y / H, h = blockIdx.y % H;
+  const int64_t p = pos[b];
+  const int64_t n = n_new ? n_new[b] : (int64_t)Tn;
+  if (p < 0 || i >= n || p + i >= cap) return;
+  const int64_t dst = ((int64_t)blockIdx.y * cap + p + i) * D;
+  const T* ks = kn + b * k_sb + h * k_sh + i * k_sr;
+  const T* vs = vn + b * v_sb + h * v_sh + i * v_sr;
+  if (vec) {
+    constexpr int V = 16 / (int)sizeof(T);
+    for (int d = threadIdx.x * V; d < D; d += 64 * V) {
+      *(uint4*)&kc[dst + d] = *(const uint4*)&ks[d];
+      *(uint4*)&vc[dst + d] = *(const uint4*)&vs[d];
+    }
+  } else {
+    for (int d = threadIdx.x; d < D; d += 64) {
+      kc[dst + d] = ks[d];
+      vc[dst + d] = vs[d];
+    }
+  }
+}
+
+void kv_append_n_launch(DT dt, void* kc, void* vc, const void* kn,
+                        const void* vn, const int64_t* pos,
+                        const int64_t* n_new, int B, int H, int T, int cap,
+                        int D, const int64_t* k_str, const int64_t* v_str,
+                        bool vec, hipStream_t s) {
+#define L(TT)                                                                 \
+  hipLaunchKernelGGL(k_kv_append_n<TT>, dim3(T, B * H), dim3(64), 0, s,       \
+                     (TT*)kc, (TT*)vc, (const TT*)kn, (const TT*)vn, pos,     \
+                     n_new, T, H, cap, D, k_str[0], k_str[1], k_str[2],       \
+                     v_str[0], v_str[1], v_str[2], vec)
+  if (dt == DT::F32) L(float);
+  else L(bf16);
+#undef L
+}
+
 }  // namespace tnn

@@ -264,6 +264,13 @@ void attn_bwd_launch(const void* q, const void* k, const void* v,
                      const int64_t* i_str, const int64_t* o_str,
                      const int64_t* do_str, const int64_t* w_str, bool causal,
                      float scale, hipStream_t s);
+// extend attention: q [B,H,T,D] view (q_str), dense [B,H,cap,D] caches, o
+// through o_str; pos / n_new are device int64 [B] (n_new may be null)
+void attn_ext_launch(const void* q, const void* k, const void* v, void* o,
+                     const int64_t* pos, const int64_t* n_new,
+                     const void* zero16, int B, int H, int T, int cap, int D,
+                     const int64_t* q_str, const int64_t* o_str, float scale,
+                     hipStream_t s);
 
 // ---- bmm.hip ---------------------------------------------------------------
 void bmm_launch(DT dt, const void* a, const void* b, void* c,
@@ -287,6 +294,12 @@ void kv_append_launch(DT dt, void* kc, void* vc, const void* kn,
                       const void* vn, const int64_t* pos, int B, int H,
                       int cap, int D, int64_t k_sb, int64_t k_sh, int64_t v_sb,
                       int64_t v_sh, hipStream_t s);
+// k_str / v_str are {batch, head, row} element strides of the new rows
+void kv_append_n_launch(DT dt, void* kc, void* vc, const void* kn,
+                        const void* vn, const int64_t* pos,
+                        const int64_t* n_new, int B, int H, int T, int cap,
+                        int D, const int64_t* k_str, const int64_t* v_str,
+                        bool vec, hipStream_t s);
 
 // ---- sample.hip (bf16 logits) ----------------------------------------------
 void sample_logits_launch(const void* logits, int64_t* ids, int R, int V,

@@ -178,6 +178,11 @@ class BatchedDecoder:
     position, returns the next-token logits ``[B, V]`` and advances the
     positions, clamped to ``seq_len - 1`` so a full row stays in bounds
     (its further outputs are meaningless). ``close()`` drops the caches.
+
+    ``open(batch)`` starts with empty rows instead of a prefill,
+    ``extend(chunks)`` appends several tokens per row at each row's own
+    position (a further turn, a refilled row, a prompt in pieces, draft
+    tokens) and ``rewind(lengths)`` sets the positions back.
     """
 
     def __init__(self, model: Sequential, seq_len: int = 1024,
@@ -212,6 +217,75 @@ class BatchedDecoder:
             p._pos_tensor = self.pos
         return out
 
+    def open(self, batch: int) -> None:
+        """Live caches for ``batch`` rows, every row at length 0, without
+        a prefill: fill them with ``extend``."""
+        if batch < 1:
+            raise ValueError("open wants at least one row")
+        self.close()
+        self.pos = torch.zeros(batch, dtype=torch.int64, device=self.device)
+        for a in self._attns:
+            a.enable_static_cache(self.seq_len, self.pos)
+        for p in self._poss:
+            p._pos_tensor = self.pos
+
+    @torch.no_grad()
+    def extend(self, chunks: List[List[int]]) -> torch.Tensor:
+        """Append ``chunks[b]`` to row b at its own position: one eager
+        forward over the right-padded ``[B, Tmax]`` batch, every row
+        attending over its own cache prefix, the chunk lengths on the
+        device. Returns the ``[B, V]`` logits at each row's last new token
+        and advances the positions by the chunk lengths. A row with an
+        empty chunk keeps its position, none of its live cache slots is
+        written, and its logits are finite but mean nothing. Raises
+        ``ValueError``, with nothing changed, if a row would pass
+        ``seq_len`` (the positions are read back: one sync). Positions
+        stay clamped to ``seq_len - 1`` like everywhere in this class, so
+        a row filled to the brim reads as one short of it."""
+        if self.pos is None:
+            raise RuntimeError("extend wants open() or prefill() first")
+        B = self.pos.numel()
+        lens = [len(c) for c in chunks]
+        if len(chunks) != B:
+            raise ValueError(f"extend wants {B} chunks, got {len(chunks)}")
+        cur = self.pos.tolist()
+        for b in range(B):
+            if cur[b] + lens[b] > self.seq_len:
+                raise ValueError(
+                    f"extend: row {b} at {cur[b]} + {lens[b]} tokens passes "
+                    f"seq_len {self.seq_len}")
+        tmax = max(1, max(lens))
+        x = torch.tensor([list(c) + [0] * (tmax - len(c)) for c in chunks],
+                         dtype=torch.int64, device=self.device)
+        n_new = torch.tensor(lens, dtype=torch.int64, device=self.device)
+        for a in self._attns:
+            a.set_extend(True, n_new)
+        for p in self._poss:
+            p._extend = True
+        try:
+            logits = self.model(x)                   # [B, Tmax, V]
+        finally:
+            for a in self._attns:
+                a.set_extend(False)
+            for p in self._poss:
+                p._extend = False
+        out = logits[torch.arange(B, device=self.device),
+                     (n_new - 1).clamp(min=0)]
+        self.pos.add_(n_new).clamp_(max=self.seq_len - 1)
+        return out
+
+    def rewind(self, lengths: List[int]) -> None:
+        """Set every row's position. Cache slots at and above a row's
+        position are dead to every kernel, so this is all it takes to drop
+        a turn or the tokens after an EOT."""
+        if self.pos is None:
+            raise RuntimeError("rewind wants open() or prefill() first")
+        if len(lengths) != self.pos.numel() or any(
+                not 0 <= n <= self.seq_len for n in lengths):
+            raise ValueError("rewind wants one length in 0..seq_len per row")
+        self.pos.copy_(torch.tensor(
+            [min(n, self.seq_len - 1) for n in lengths], dtype=torch.int64))
+
     def forward_token(self, tok: torch.Tensor) -> torch.Tensor:
         """Logits ``[B, V]`` for the ``[B, 1]`` tokens at the current
         positions; does not advance."""
@@ -240,6 +314,71 @@ MAX_DECODE_BATCH = 16   # rows of one captured step (the skinny GEMM's M)
 
 
 @torch.no_grad()
+def _decode_loop(dec: BatchedDecoder, logits: torch.Tensor, n_steps: int,
+                 temp: float, top_k: int, top_p: float, seed: int,
+                 is_greedy: bool, use_graph: Optional[bool]
+                 ) -> List[List[int]]:
+    """``n_steps`` tokens per row on an open decoder whose rows have just
+    produced ``logits``: first pick, then the single-token step -- forward,
+    on-device sampling, feed-back, id recording, position advance --
+    captured once and replayed (or run eagerly), and one read-back of the
+    ids ``[B][n_steps]``. Leaves every position advanced by ``n_steps -
+    1``: the last token of a row is sampled but not fed."""
+    from ..ops import sample_logits
+    device = dec.device
+    B = logits.shape[0]
+    graph_ok = device.type == "cuda" and (
+        is_greedy or logits.dtype == torch.bfloat16)
+    graphed = graph_ok if use_graph is None else use_graph
+    step_t = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def pick(lg):
+        return sample_logits(lg, temp, top_k, top_p, seed, step_t)
+
+    # two spare columns: the graph warm-up steps record past the end
+    ids_buf = torch.zeros(B, n_steps + 2, dtype=torch.int64,
+                          device=device)
+    first = pick(logits)
+    ids_buf[:, 0] = first
+    static_tok = first.reshape(B, 1).clone()
+    step_t.fill_(1)
+
+    def step():
+        nxt = pick(dec.forward_token(static_tok)).reshape(B, 1)
+        ids_buf.index_copy_(1, step_t, nxt)
+        static_tok.copy_(nxt)
+        step_t.add_(1)
+        dec.advance()
+
+    state = (dec.pos, static_tok, ids_buf, step_t)
+    n_replay = n_steps - 1
+    if graphed and n_replay > 0:
+        saved = [t.clone() for t in state]
+
+        def restore():
+            for t, s0 in zip(state, saved):
+                t.copy_(s0)
+
+        stream = torch.cuda.Stream()
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            for _ in range(2):  # warmup; stale cache rows stay masked
+                step()
+        torch.cuda.current_stream().wait_stream(stream)
+        restore()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            step()
+        restore()
+        for _ in range(n_replay):
+            graph.replay()
+    else:
+        for _ in range(n_replay):
+            step()
+    return ids_buf[:, :n_steps].tolist()
+
+
+@torch.no_grad()
 def generate_batch(model: Sequential, prompts: List[List[int]],
                    max_new_tokens: int = 50, seq_len: int = 1024,
                    eot_token: Optional[int] = 50256,
@@ -259,7 +398,6 @@ def generate_batch(model: Sequential, prompts: List[List[int]],
     EOT is post-hoc truncation per row, as in ``generate_graphed``. More
     than 16 prompts run in chunks of 16. ``use_graph=False`` runs the
     identical tensor-driven step eagerly (CPU-testable path)."""
-    from ..ops import sample_logits
     prompts = [list(p) for p in prompts]
     if any(len(p) == 0 for p in prompts):
         raise ValueError("generate_batch: empty prompt")
@@ -280,57 +418,9 @@ def generate_batch(model: Sequential, prompts: List[List[int]],
         dec = BatchedDecoder(model, seq_len, device)
         try:
             logits = dec.prefill([prompts[i] for i in rows])
-            B = len(rows)
             n_steps = max(n_new[i] for i in rows)
-            graph_ok = device.type == "cuda" and (
-                is_greedy or logits.dtype == torch.bfloat16)
-            graphed = graph_ok if use_graph is None else use_graph
-            step_t = torch.zeros(1, dtype=torch.int64, device=device)
-
-            def pick(lg):
-                return sample_logits(lg, temp, top_k, top_p, seed, step_t)
-
-            # two spare columns: the graph warm-up steps record past the end
-            ids_buf = torch.zeros(B, n_steps + 2, dtype=torch.int64,
-                                  device=device)
-            first = pick(logits)
-            ids_buf[:, 0] = first
-            static_tok = first.reshape(B, 1).clone()
-            step_t.fill_(1)
-
-            def step():
-                nxt = pick(dec.forward_token(static_tok)).reshape(B, 1)
-                ids_buf.index_copy_(1, step_t, nxt)
-                static_tok.copy_(nxt)
-                step_t.add_(1)
-                dec.advance()
-
-            state = (dec.pos, static_tok, ids_buf, step_t)
-            n_replay = n_steps - 1
-            if graphed and n_replay > 0:
-                saved = [t.clone() for t in state]
-
-                def restore():
-                    for t, s0 in zip(state, saved):
-                        t.copy_(s0)
-
-                stream = torch.cuda.Stream()
-                stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(stream):
-                    for _ in range(2):  # warmup; stale cache rows stay masked
-                        step()
-                torch.cuda.current_stream().wait_stream(stream)
-                restore()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    step()
-                restore()
-                for _ in range(n_replay):
-                    graph.replay()
-            else:
-                for _ in range(n_replay):
-                    step()
-            new = ids_buf[:, :n_steps].tolist()
+            new = _decode_loop(dec, logits, n_steps, temp, top_k, top_p,
+                               seed, is_greedy, use_graph)
             for r, i in enumerate(rows):
                 ids = new[r][:n_new[i]]
                 if eot_token is not None and eot_token in ids:
@@ -342,3 +432,108 @@ def generate_batch(model: Sequential, prompts: List[List[int]],
     for c0 in range(0, len(live), MAX_DECODE_BATCH):
         run_chunk(live[c0:c0 + MAX_DECODE_BATCH])
     return out
+
+
+class DecodeSession:
+    """Multi-turn batched decode over live KV caches: up to 16 rows, each
+    with its own growing context. ``generate(chunks)`` appends
+    ``chunks[b]`` to row b's context with one ``extend`` forward (no
+    re-prefill of what was said before), decodes all rows together with
+    the captured single-token step of ``generate_batch`` and returns the
+    new tokens per row, EOT-truncated.
+
+    A row with an empty chunk is idle in that call: it returns ``[]``, its
+    context and live cache are unchanged, and its position is restored
+    after the shared steps (which write only dead slots above it). An
+    active row yields ``min(max_new_tokens, seq_len - len(context) -
+    len(chunk))`` tokens. The last sampled token of a row is not in the
+    cache yet: the session keeps ``pos_b = len(context_b) - 1`` and feeds
+    that pending token in front of the next chunk. Rewinding to that
+    position also drops whatever the shared steps wrote past a row's EOT.
+
+    Greedy contract: row b's result equals the new tokens of
+    ``generate_batch(model, [context_b + chunk_b], ...)`` with the same
+    ``max_new_tokens``, ``seq_len`` and ``eot_token``.
+
+    ``context`` is the host copy of every row's tokens; ``rewind(lengths)``
+    cuts contexts back; ``reset(rows)`` frees rows (all when None) by
+    setting their length to 0; ``close()`` drops the caches."""
+
+    def __init__(self, model: Sequential, batch: int, seq_len: int = 1024,
+                 device: Optional[torch.device] = None):
+        if not 1 <= batch <= MAX_DECODE_BATCH:
+            raise ValueError(
+                f"DecodeSession wants 1..{MAX_DECODE_BATCH} rows, got {batch}")
+        self.seq_len = seq_len
+        self.context: List[List[int]] = [[] for _ in range(batch)]
+        self._dec = BatchedDecoder(model, seq_len, device)
+        self._dec.open(batch)
+
+    def _sync_positions(self) -> None:
+        self._dec.rewind([max(len(c) - 1, 0) for c in self.context])
+
+    @torch.no_grad()
+    def generate(self, chunks: List[List[int]], max_new_tokens: int = 50,
+                 eot_token: Optional[int] = 50256, greedy: bool = True,
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                 seed: int = 0, use_graph: Optional[bool] = None
+                 ) -> List[List[int]]:
+        if self._dec.pos is None:
+            raise RuntimeError("DecodeSession is closed")
+        chunks = [list(c) for c in chunks]
+        B = len(self.context)
+        if len(chunks) != B:
+            raise ValueError(f"generate wants {B} chunks, got {len(chunks)}")
+        if not (0.0 < top_p <= 1.0):
+            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+        if top_k < 0:
+            raise ValueError(f"top_k must be >= 0, got {top_k}")
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0, got {temperature}")
+        for b in range(B):
+            if len(self.context[b]) + len(chunks[b]) > self.seq_len:
+                raise ValueError(
+                    f"generate: row {b} would pass seq_len {self.seq_len}")
+        temp = 0.0 if greedy else float(temperature)
+        is_greedy = temp == 0.0 or top_k == 1
+        n_new = [min(max_new_tokens, self.seq_len - len(self.context[b])
+                     - len(chunks[b])) if chunks[b] else 0 for b in range(B)]
+        out: List[List[int]] = [[] for _ in range(B)]
+        if not any(chunks):
+            return out
+        # the pending (sampled, not yet cached) token leads the chunk
+        feeds = [self.context[b][-1:] + chunks[b] if chunks[b] else []
+                 for b in range(B)]
+        try:
+            logits = self._dec.extend(feeds)
+            n_steps = max(n_new)
+            if n_steps > 0:
+                new = _decode_loop(self._dec, logits, n_steps, temp, top_k,
+                                   top_p, seed, is_greedy, use_graph)
+                for b in range(B):
+                    ids = new[b][:max(n_new[b], 0)]
+                    if eot_token is not None and eot_token in ids:
+                        ids = ids[:ids.index(eot_token) + 1]
+                    out[b] = ids
+            for b in range(B):
+                self.context[b] += chunks[b] + out[b]
+        finally:
+            self._sync_positions()
+        return out
+
+    def rewind(self, lengths: List[int]) -> None:
+        """Cut row b's context back to its first ``lengths[b]`` tokens
+        (drops a turn; the cache slots behind them go dead)."""
+        if len(lengths) != len(self.context) or any(
+                not 0 <= n <= len(c) for n, c in zip(lengths, self.context)):
+            raise ValueError("rewind wants one length within each context")
+        self.context = [c[:n] for c, n in zip(self.context, lengths)]
+        self._sync_positions()
+
+    def reset(self, rows: Optional[List[int]] = None) -> None:
+        for b in (range(len(self.context)) if rows is None else rows):
+            self.context[b] = []
+        self._sync_positions()
+
+    def close(self) -> None:
+        self._dec.close()

@@ -299,6 +299,46 @@ class _MHABase(Layer):
         self._kv_cache = {"k": None, "v": None, "len": 0, "cap": max_len,
                           "pos_t": pos_t}
 
+    def set_extend(self, on: bool, n_new: Optional[torch.Tensor] = None):
+        """Extend mode of the per-sequence static cache: a forward over
+        ``[B, T]`` appends row b's first ``n_new[b]`` tokens (all T when
+        None) at ``pos_t[b]`` and attends each over its own prefix
+        (``_extend_forward``). Off, multi-token input keeps the prefill
+        route, which writes at one shared host position."""
+        c = self._kv_cache
+        assert c is not None and "pos_t" in c and c["pos_t"].numel() >= 1
+        c["extend"], c["n_new"] = on, n_new if on else None
+
+    def _extending(self) -> bool:
+        c = self._kv_cache
+        return c is not None and bool(c.get("extend"))
+
+    def _extend_forward(self, x, residual=None, ln=None):
+        """One merged-QKV projection, one multi-row cache append, extend
+        attention over each sequence's own prefix, view-only merge."""
+        c = self._kv_cache
+        b, s, d = x.shape
+        h, hd = self.num_heads, self.head_dim
+        if self._wqkv is None:
+            self._build_qkv_merge()
+        if s == 1 and x.is_cuda and not x.requires_grad:
+            qkv = ops.linear(x, self._wqkv, self._bqkv, ln=ln)
+        else:
+            if ln is not None:
+                x = ops.layer_norm(x, *ln)
+            qkv = ops.linear(x, self._wqkv, self._bqkv)
+        q, k, v = (t.view(b, s, h, hd).transpose(1, 2)
+                   for t in qkv.detach().split(d, dim=-1))
+        if c["k"] is None:
+            c["k"] = torch.zeros(b, h, c["cap"], hd, device=x.device,
+                                 dtype=k.dtype)
+            c["v"] = torch.zeros_like(c["k"])
+        ops.kv_append_n(c["k"], c["v"], k, v, c["pos_t"], c["n_new"])
+        o = ops.attention_extend(q, c["k"], c["v"], c["pos_t"], c["n_new"],
+                                 hd ** -0.5)
+        o = o.transpose(1, 2).reshape(b, s, d)   # [B,T,H,D] memory: a view
+        return ops.linear(o, self.wo, self.bo, residual=residual)
+
     def _project(self, x, ln=None):
         b, s, d = x.shape
         h, hd = self.num_heads, self.head_dim
@@ -412,6 +452,8 @@ class AttentionBlock(_MHABase):
 
     def forward(self, x, residual=None, ln=None):
         b, s, _ = x.shape
+        if self._extending():
+            return self._extend_forward(x, residual, ln)
         q, k, v = self._project(x, ln=ln)
         if self._kv_cache is not None:
             o = self._cached_attention(q, k, v)
@@ -427,6 +469,8 @@ class FlashAttentionBlock(_MHABase):
 
     def forward(self, x, residual=None, ln=None):
         b, s, _ = x.shape
+        if self._extending():
+            return self._extend_forward(x, residual, ln)
         if self._kv_cache is not None:
             q, k, v = self._project(x, ln=ln)
             o = self._cached_attention(q, k, v)

@@ -339,9 +339,15 @@ class PositionalEmbedding(Layer):
     # device int64 [1], or [B] with one position per sequence (ragged
     # batched decode): graph-capturable position
     _pos_tensor = None
+    # extend mode (BatchedDecoder.extend): token i of row b sits at
+    # _pos_tensor[b] + i; padding past max_len reuses the last row
+    _extend = False
 
     def forward(self, x):
         s = x.shape[-2]
+        if self._extend and self._pos_tensor is not None:
+            idx = self._pos_tensor[:, None] + torch.arange(s, device=x.device)
+            return x + self.weight[idx.clamp(max=self.max_len - 1)]
         if self._pos_tensor is not None and s == 1:
             pe = self.weight.index_select(0, self._pos_tensor)
             if self._pos_tensor.numel() > 1:

@@ -28,6 +28,8 @@ from .functional import (
     sdpa_materialized,
     attention_decode,
     kv_append,
+    attention_extend,
+    kv_append_n,
     sample_logits,
     scaled_softmax,
     group_norm,
@@ -53,6 +55,8 @@ __all__ = [
     "sdpa_materialized",
     "attention_decode",
     "kv_append",
+    "attention_extend",
+    "kv_append_n",
     "sample_logits",
     "scaled_softmax",
     "group_norm",

@@ -1005,6 +1005,76 @@ def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
     v_cache[rows, :, pos] = v_new[:, :, 0]
 
 
+def _extend_extent(pos: torch.Tensor, n_new: Optional[torch.Tensor],
+                   T: int, cap: int):
+    """(p0, n) of the extend rule: p0 = pos clamped into [0, cap], n =
+    n_new (T when absent) clamped into [0, min(T, cap - p0)]."""
+    p0 = pos.clamp(0, cap)
+    n = torch.full_like(p0, T) if n_new is None else n_new.clamp(min=0)
+    return p0, torch.minimum(n, (cap - p0).clamp(max=T))
+
+
+def attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, pos: torch.Tensor,
+                     n_new: Optional[torch.Tensor] = None,
+                     scale: Optional[float] = None) -> torch.Tensor:
+    """Attention of T new query rows per sequence against that sequence's
+    own cache prefix (inference only). q ``[B,H,T,D]`` (unit d-stride; the
+    head slices of a merged projection are fine), caches ``[B,H,cap,D]``
+    with the new rows already appended, ``pos`` / ``n_new`` int64 ``[B]``
+    on the caches' device. Row ``i < n_new[b]`` of sequence b sits at
+    position ``pos[b] + i`` and sees keys ``j <= pos[b] + i``; rows
+    ``>= n_new[b]`` come back zero; cache slots ``>= pos[b] + n_new[b]``
+    never enter the result, whatever they hold. Returns ``[B,H,T,D]`` laid
+    out ``[B,T,H,D]``, so ``o.transpose(1, 2)`` is contiguous. CUDA bf16
+    with D in {64, 128} runs the flash extend kernel; everything else the
+    torch form of the same rule."""
+    B, H, T, D = q.shape
+    cap = k_cache.shape[2]
+    if scale is None:
+        scale = D ** -0.5
+    if q.is_cuda and q.dtype == torch.bfloat16 and D in (64, 128):
+        return _C.ext().attn_extend(q, k_cache, v_cache, pos, n_new, scale)
+    p0, n = _extend_extent(pos, n_new, T, cap)
+    i = torch.arange(T, device=q.device)
+    j = torch.arange(cap, device=q.device)
+    live_k = j[None, :] < (p0 + n)[:, None]                       # [B, cap]
+    vis = (j[None, None, :] <= (p0[:, None] + i[None, :])[:, :, None]) \
+        & live_k[:, None, :]                                      # [B, T, cap]
+    live_q = i[None, :] < n[:, None]                              # [B, T]
+    s = (q.float() @ k_cache.float().transpose(-1, -2)) * scale
+    s = s.masked_fill(~vis[:, None], float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    p = torch.where(live_q[:, None, :, None], p, torch.zeros_like(p))
+    v = torch.where(live_k[:, None, :, None], v_cache.float(),
+                    torch.zeros((), device=q.device))
+    o = torch.empty(B, T, H, D, dtype=q.dtype, device=q.device)
+    o = o.permute(0, 2, 1, 3)
+    o.copy_(p @ v)
+    return o
+
+
+def kv_append_n(k_cache: torch.Tensor, v_cache: torch.Tensor,
+                k_new: torch.Tensor, v_new: torch.Tensor, pos: torch.Tensor,
+                n_new: Optional[torch.Tensor] = None) -> None:
+    """Write sequence b's new K/V rows ``i < n_new[b]`` (all T when absent)
+    of ``[B,H,T,D]`` into the ``[B,H,cap,D]`` caches at slot ``pos[b] +
+    i``, in place. Rows that would land at ``>= cap`` and every row of a
+    negative ``pos[b]`` are dropped. One launch on GPU (fp32 / bf16), an
+    index_put elsewhere."""
+    if k_cache.is_cuda and k_cache.dtype in (torch.float32, torch.bfloat16):
+        _C.ext().kv_append_n(k_cache, v_cache, k_new, v_new, pos, n_new)
+        return
+    T, cap = k_new.shape[2], k_cache.shape[2]
+    i = torch.arange(T, device=k_cache.device)
+    slot = pos[:, None] + i[None, :]                               # [B, T]
+    n = torch.full_like(pos, T) if n_new is None else n_new
+    ok = (pos[:, None] >= 0) & (i[None, :] < n[:, None]) & (slot < cap)
+    bi, ti = ok.nonzero(as_tuple=True)
+    k_cache[bi, :, slot[bi, ti]] = k_new[bi, :, ti]
+    v_cache[bi, :, slot[bi, ti]] = v_new[bi, :, ti]
+
+
 # ---------------------------------------------------------------------------
 # sampling (temperature / top-k / top-p)
 # ---------------------------------------------------------------------------
