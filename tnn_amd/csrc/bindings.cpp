@@ -35,6 +35,12 @@ static DT dt_of(const at::Tensor& t) {
   TORCH_CHECK((t).is_cuda(), #t " must be on GPU");             \
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
+// The GEMM entry points raise on an empty operand instead of launching a
+// zero-sized grid (an invalid launch) or returning an epilogue of nothing.
+#define CHECK_NONEMPTY(fn, M, N, K)                                   \
+  TORCH_CHECK((M) >= 1 && (N) >= 1 && (K) >= 1, fn ": empty operand", \
+              " (M = ", (M), ", N = ", (N), ", K = ", (K), ")")
+
 // ---- elementwise -----------------------------------------------------------
 at::Tensor act_fwd(const at::Tensor& x, int64_t kind) {
   CHECK_IN(x);
@@ -163,10 +169,12 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
   TORCH_CHECK(a.scalar_type() == b.scalar_type(), "gemm dtype mismatch ",
               a.scalar_type(), " vs ", b.scalar_type());
   int M = a.size(0), K = a.size(1), N = b.size(1);
+  CHECK_NONEMPTY("gemm", M, N, K);
   auto c = at::empty({M, N}, a.options());
   const void* bp = nullptr;
   if (bias.has_value()) {
     // the kernels read bias as a's element type, N entries
+    TORCH_CHECK(bias->is_cuda(), "gemm bias must be on GPU");
     TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
                 bias->scalar_type() == a.scalar_type(),
                 "gemm bias must be contiguous [", N, "] ", a.scalar_type(),
@@ -175,6 +183,7 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
   }
   const void* rp = nullptr;
   if (residual.has_value()) {
+    TORCH_CHECK(residual->is_cuda(), "gemm residual must be on GPU");
     TORCH_CHECK(residual->is_contiguous() &&
                 residual->scalar_type() == a.scalar_type() &&
                 residual->numel() == (int64_t)M * N,
@@ -188,6 +197,15 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b,
                 ln_gamma->scalar_type() == at::kFloat &&
                 ln_beta->scalar_type() == at::kFloat,
                 "fused ln: decode GEMV only, fp32 gamma/beta");
+    // the kernel reads K floats from each, on the device
+    TORCH_CHECK(ln_gamma->is_cuda() && ln_gamma->is_contiguous() &&
+                ln_gamma->numel() == K,
+                "gemm ln_gamma must be a contiguous GPU tensor of [", K,
+                "], got ", ln_gamma->sizes(), " on ", ln_gamma->device());
+    TORCH_CHECK(ln_beta->is_cuda() && ln_beta->is_contiguous() &&
+                ln_beta->numel() == K,
+                "gemm ln_beta must be a contiguous GPU tensor of [", K,
+                "], got ", ln_beta->sizes(), " on ", ln_beta->device());
     lng = ln_gamma->data_ptr<float>();
     lnb = ln_beta->data_ptr<float>();
   }
@@ -277,7 +295,7 @@ at::Tensor gemm_skinny(const at::Tensor& a, const at::Tensor& b,
   const int M = a.size(0), K = a.size(1), N = b.size(1);
   TORCH_CHECK(M >= 1 && M <= SKINNY_MAX_M, "gemm_skinny wants 1 <= M <= ",
               SKINNY_MAX_M, ", got M = ", M);
-  TORCH_CHECK(K >= 1 && N >= 1, "gemm_skinny: empty operand");
+  CHECK_NONEMPTY("gemm_skinny", M, N, K);
   auto c = at::empty({M, N}, a.options());
   const void* bp = nullptr;
   if (bias.has_value()) {
@@ -323,7 +341,12 @@ at::Tensor gemm_nt(const at::Tensor& a, const at::Tensor& b) {
   CHECK_IN(b);
   TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1),
               "gemm_nt shapes ", a.sizes(), " @ ", b.sizes(), "^T");
+  // both operands are read as a's element type
+  TORCH_CHECK(a.scalar_type() == b.scalar_type(),
+              "gemm_nt dtype mismatch: b is ", b.scalar_type(), ", a is ",
+              a.scalar_type());
   int M = a.size(0), K = a.size(1), N = b.size(0);
+  CHECK_NONEMPTY("gemm_nt", M, N, K);
   auto c = at::empty({M, N}, a.options());
   at::Tensor ws;
   if (gemm32_enabled() && dt_of(a) == DT::BF16 && K % 8 == 0 &&
@@ -355,7 +378,11 @@ at::Tensor gemm_tn(const at::Tensor& a, const at::Tensor& b, bool out_in_dt) {
   CHECK_IN(b);
   TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(0) == b.size(0),
               "gemm_tn shapes ", a.sizes(), "^T @ ", b.sizes());
+  TORCH_CHECK(a.scalar_type() == b.scalar_type(),
+              "gemm_tn dtype mismatch: b is ", b.scalar_type(), ", a is ",
+              a.scalar_type());
   int M = a.size(0), K = a.size(1), N = b.size(1);
+  CHECK_NONEMPTY("gemm_tn", M, N, K);
   DT out_dt = out_in_dt ? dt_of(a) : DT::F32;
   auto c = at::empty({K, N}, out_dt == DT::F32
                                  ? a.options().dtype(at::kFloat)
@@ -1174,6 +1201,8 @@ at::Tensor bmm(const at::Tensor& a_in, const at::Tensor& b_in) {
   at::Tensor a = norm(a_in), b = norm(b_in);
   const int64_t batch = a.size(0), M = a.size(1), K = a.size(2), N = b.size(2);
   TORCH_CHECK(b.size(0) == batch && b.size(1) == K, "bmm shape mismatch");
+  TORCH_CHECK(batch >= 1, "bmm: empty operand (batch = 0)");
+  CHECK_NONEMPTY("bmm", M, N, K);
   TORCH_CHECK(batch <= 65535, "bmm batch > 65535");
   bool ta, tb;
   int64_t lda, ldb;

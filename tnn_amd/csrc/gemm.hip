@@ -177,7 +177,8 @@ __global__ void k_gemm(const T* __restrict__ A, const T* __restrict__ B,
 
   for (int k0 = 0; k0 < K; k0 += BK) {
     // A[M,K] and (TRANS_B) B[N,K] rows are already the image rows. GLDS:
-    // K % V == 0 and 16B-aligned A guaranteed by the launcher.
+    // K % V == 0 and 16B-aligned A (and B, when TRANS_B) guaranteed by
+    // the launcher.
     if constexpr (GLDS)
       glds_stage_rows<T, BM>(As, wc, A, zero16, m0, M, K, k0, K);
     else
@@ -1470,13 +1471,16 @@ void gemm_launch(DT dt, const void* a, const void* b, const void* bias,
       return;
     }
     dim3 grid(ceil_div(M, BM), ceil_div(N, BN));
-    const bool g = K % vec_elems(dt) == 0 && ptr_aligned16(a);
+    // glds stages 16-byte vectors straight from global memory: with
+    // trans_b it reads B's rows that way too, so B must be aligned as well
+    const bool g = K % vec_elems(dt) == 0 && ptr_aligned16(a) &&
+                   (!trans_b || ptr_aligned16(b));
     auto launch = [&](auto kern) {
       hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, s, A, B,
                          (const T*)bias, (T*)c, (const T*)zero16,
                          (const T*)resid, M, N, K, act_kind);
     };
-    if (trans_b && g && K <= 3072 && ptr_aligned16(b))
+    if (trans_b && g && K <= 3072)
       launch(k_gemm_nt_db<T>);
     else if (trans_b)
       launch(g ? k_gemm<T, true, true> : k_gemm<T, true, false>);
