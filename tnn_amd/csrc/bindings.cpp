@@ -529,6 +529,29 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H,
   return dx;
 }
 
+// which kernel conv2d_fwd / conv2d_fwd_stats and conv2d_dgrad launch for these
+// arguments (tests and profile notes name the route with these)
+std::string conv2d_fwd_route_name(const at::Tensor& x, const at::Tensor& w,
+                                  int64_t sh, int64_t sw, int64_t ph,
+                                  int64_t pw, bool stats) {
+  CHECK_IN(x);
+  CHECK_IN(w);
+  auto cs = conv_shape(x, w.size(2), w.size(3), w.size(0), w.size(1), sh, sw,
+                       ph, pw);
+  return conv2d_fwd_route(dt_of(x), x.data_ptr(), cs, stats);
+}
+
+std::string conv2d_dgrad_route_name(const at::Tensor& dy,
+                                    const at::Tensor& w, int64_t H, int64_t W,
+                                    int64_t sh, int64_t sw, int64_t ph,
+                                    int64_t pw) {
+  CHECK_IN(dy);
+  CHECK_IN(w);
+  auto cs = conv_shape_out(dy.size(0), H, W, w.size(2), w.size(3), w.size(0),
+                           w.size(1), sh, sw, ph, pw, dy.size(1), dy.size(2));
+  return conv2d_dgrad_route(dt_of(dy), dy.data_ptr(), cs);
+}
+
 // returns [KH*KW*Cin (+1 with bias), Cout]: dw rows, then the bias-gradient row
 static at::Tensor conv2d_wgrad_rows(const at::Tensor& x, const at::Tensor& dy,
                                     int64_t KH, int64_t KW, int64_t sh,
@@ -1502,6 +1525,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &tnn::conv2d_fwd);
   m.def("conv2d_fwd_stats", &tnn::conv2d_fwd_stats);
   m.def("conv2d_dgrad", &tnn::conv2d_dgrad);
+  m.def("conv2d_fwd_route", &tnn::conv2d_fwd_route_name);
+  m.def("conv2d_dgrad_route", &tnn::conv2d_dgrad_route_name);
   m.def("conv2d_wgrad", &tnn::conv2d_wgrad);
   m.def("conv2d_wgrad_bias", &tnn::conv2d_wgrad_bias);
   m.def("bn_fwd_train", &tnn::bn_fwd_train, py::arg("x"), py::arg("gamma"),

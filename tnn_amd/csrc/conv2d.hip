@@ -244,10 +244,10 @@ DEV void stage_b_transposed(T* Bs, RowFn&& rowptr, int ncols, int n0, int k0,
 // instruction selection of the DMA-staged kernels' epilogues.
 
 // fwd: y = act(acc + bias), cast store
-template <typename T>
-DEV void conv_fwd_store(const WaveCoord& wc, f32x4 acc[FM][FN], const T* bias,
-                        T* Y, const ConvShape& cs, int act_kind, int m0,
-                        int n0, int M) {
+template <typename T, typename S>
+DEV void conv_fwd_store(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN],
+                        const T* bias, T* Y, const ConvShape& cs, int act_kind,
+                        int m0, int n0, int M) {
   epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
     if (row < M && col < cs.Cout) {
       if (bias) v += VecIO<T>::to_f32(bias[col]);
@@ -261,10 +261,11 @@ DEV void conv_fwd_store(const WaveCoord& wc, f32x4 acc[FM][FN], const T* bias,
 // accumulators (post-bias, linear act only): saves the BN stats pass's full
 // read of y. C/D fragment col = lane&15; lanes {l, l+16, l+32, l+48} share
 // a column -> two shfl_xor folds, then one atomic per (block, col).
-template <typename T>
-DEV void conv_fwd_stats(const WaveCoord& wc, f32x4 acc[FM][FN],
+template <typename T, typename S>
+DEV void conv_fwd_stats(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN],
                         const T* bias_p, float* stats, const ConvShape& cs,
                         int m0, int n0, int M) {
+  constexpr int FM = S::FM, FN = S::FN;
   float* ssum = stats;
   float* ssumsq = stats + cs.Cout;
   const int cr = (wc.lane >> 4) * 4;
@@ -300,8 +301,8 @@ DEV void conv_fwd_stats(const WaveCoord& wc, f32x4 acc[FM][FN],
 }
 
 // dgrad: cast store of a class's rows to their dx pixels
-template <bool POW2, typename T, bool S2>
-DEV void dgrad_store(const WaveCoord& wc, f32x4 acc[FM][FN], T* DX,
+template <bool POW2, typename T, bool S2, typename S>
+DEV void dgrad_store(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN], T* DX,
                      const ConvShape& cs, const DgradClass<S2>& dc, int m0,
                      int n0) {
   epilogue_visit(wc, acc, m0, n0, [&](int row, int col, float v) {
@@ -361,16 +362,19 @@ DEV void wgrad_colsum_store(float* out, const ConvShape& cs, int Kout, int n0,
 // compiler, which drains the DMAs before them as it always did. Chunk, k-step
 // and MFMA order are those of the single-buffer kernels: the accumulators are
 // bitwise the same.
-template <bool DB, typename T, typename RowFn, typename TapFn, typename AtFn>
+// The tile shape S comes with wc: the images are [S::BM][BK] and [S::BN][BK],
+// filled by S::BM/32 + S::BN/32 bf16 DMA instructions per wave and chunk.
+template <bool DB, typename T, typename S, typename RowFn, typename TapFn,
+          typename AtFn>
 DEV void conv_db_kloop(T* As0, T* As1, T* Bs0, T* Bs1,
-                       const WaveCoord& wc, f32x4 acc[FM][FN],
+                       const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN],
                        const T* __restrict__ asrc, int lgSW, int lgC,
                        const T* __restrict__ bsrc, int64_t bstride,
                        int brows, int m0, int n0, int K,
                        const T* __restrict__ zero16, RowFn&& row,
                        TapFn&& tap, AtFn&& at) {
-  constexpr int NA = glds_count<T, BM>();   // A glds per wave
-  constexpr int NB = glds_count<T, BN>();   // B glds per wave
+  constexpr int NA = glds_count<T, S::BM>();   // A glds per wave
+  constexpr int NB = glds_count<T, S::BN>();   // B glds per wave
   constexpr int NPER = NA + NB;
   const int wid = __builtin_amdgcn_readfirstlane(wc.wid);
   const bool uni = lgC >= 6;   // C % BK == 0: one tap per chunk
@@ -485,7 +489,7 @@ DEV void conv_db_kloop(T* As0, T* As1, T* Bs0, T* Bs1,
 // next chunk's DMAs overlap the current chunk's MFMAs. Counted
 // s_waitcnt vmcnt + raw s_barrier per the CDNA4 glds idiom -- a
 // __syncthreads() here would drain the in-flight next-chunk DMAs.
-template <typename T, bool STATS, bool DB>
+template <typename T, bool STATS, bool DB, typename S = TileStd>
 DEV void conv_fwd_glds_tile(const T* __restrict__ X,
                             const T* __restrict__ WT2,
                             const T* __restrict__ bias, T* __restrict__ Y,
@@ -495,10 +499,10 @@ DEV void conv_fwd_glds_tile(const T* __restrict__ X,
   const int K = cs.KH * cs.KW * cs.Cin;
   int tm_, tn_;
   conv_tile_order(cs, tm_, tn_);
-  const int m0 = tm_ * BM;
-  const int n0 = tn_ * BN;
-  const WaveCoord wc;
-  f32x4 acc[FM][FN] = {};
+  const int m0 = tm_ * S::BM;
+  const int n0 = tn_ * S::BN;
+  const WaveCoordT<S> wc;
+  f32x4 acc[S::FM][S::FN] = {};
 
   auto row = [&](int gm, int64_t& noff, int& p, int& q) {
     const int n = gm >> cs.d_ohow.lg;
@@ -520,13 +524,13 @@ DEV void conv_fwd_glds_tile(const T* __restrict__ X,
   };
   if constexpr (DB) {
     // one LDS object per buffer, named statically in the 2x-unrolled loop
-    __shared__ alignas(16) T As0[BM * BK], As1[BM * BK];
-    __shared__ alignas(16) T Bs0[BN * BK], Bs1[BN * BK];
+    __shared__ alignas(16) T As0[S::BM * BK], As1[S::BM * BK];
+    __shared__ alignas(16) T Bs0[S::BN * BK], Bs1[S::BN * BK];
     conv_db_kloop<true>(As0, As1, Bs0, Bs1, wc, acc, X, cs.d_w.lg,
                         cs.d_cin.lg, WT2, (int64_t)K, cs.Cout, m0, n0, K,
                         zero16, row, tap, at);
   } else {
-    __shared__ alignas(16) T As0[BM * BK], Bs0[BN * BK];
+    __shared__ alignas(16) T As0[S::BM * BK], Bs0[S::BN * BK];
     conv_db_kloop<false>(As0, As0, Bs0, Bs0, wc, acc, X, cs.d_w.lg,
                          cs.d_cin.lg, WT2, (int64_t)K, cs.Cout, m0, n0, K,
                          zero16, row, tap, at);
@@ -560,6 +564,38 @@ __global__ void k_conv_fwd_sb(const bf16* __restrict__ X,
                               int act_kind, float* __restrict__ stats) {
   conv_fwd_glds_tile<bf16, STATS, false>(X, WT2, bias, Y, zero16, cs, act_kind,
                                          stats);
+}
+
+// the 128x128 tile (TileWide) of the two kernels above, for Cout % 128 == 0:
+// 32 KB of images per 2.1 MFLOP chunk where the 128x64 tile stages 24 KB per
+// 1.05 MFLOP, and the im2col gather with its address decode is fetched once
+// per 128 output channels. Same images, chunk order and MFMA sequence per
+// output element, so y is bitwise that of the 128x64 kernels. 64 accumulator
+// registers; the double buffer holds 64 KB LDS (2 blocks per CU), the single
+// buffer 32 KB and is capped at the 168 registers of 3 waves per SIMD.
+template <bool STATS>
+__launch_bounds__(THREADS, 2)
+__global__ void k_conv_fwd_db_wide(const bf16* __restrict__ X,
+                                   const bf16* __restrict__ WT2,
+                                   const bf16* __restrict__ bias,
+                                   bf16* __restrict__ Y,
+                                   const bf16* __restrict__ zero16,
+                                   ConvShape cs, int act_kind,
+                                   float* __restrict__ stats) {
+  conv_fwd_glds_tile<bf16, STATS, true, TileWide>(X, WT2, bias, Y, zero16, cs,
+                                                  act_kind, stats);
+}
+template <bool STATS>
+__launch_bounds__(THREADS, 3)
+__global__ void k_conv_fwd_sb_wide(const bf16* __restrict__ X,
+                                   const bf16* __restrict__ WT2,
+                                   const bf16* __restrict__ bias,
+                                   bf16* __restrict__ Y,
+                                   const bf16* __restrict__ zero16,
+                                   ConvShape cs, int act_kind,
+                                   float* __restrict__ stats) {
+  conv_fwd_glds_tile<bf16, STATS, false, TileWide>(X, WT2, bias, Y, zero16, cs,
+                                                   act_kind, stats);
 }
 
 // ---------------------------------------------------------------------------
@@ -697,27 +733,28 @@ __global__ void k_conv_dgrad(const T* __restrict__ DY, const T* __restrict__ WT,
 // double-buffered pure-glds dgrad (see k_conv_fwd_db; all-pow2 shapes only):
 // the weight comes pre-transposed to [Cin, KH*KW*Cout] so B rows are
 // k-contiguous; with S2 the compacted parity-class k index remaps into the
-// full column space.
-template <typename T, bool S2 = false, bool S1 = false>
-__launch_bounds__(THREADS)
-__global__ void k_conv_dgrad_db(const T* __restrict__ DY,
-                                const T* __restrict__ WT2D,
-                                T* __restrict__ DX,
-                                const T* __restrict__ zero16, ConvShape cs) {
+// full column space. One body for the 128x64 kernel and the wide forms, on
+// two buffer pairs (DB) or one; its pointers take their __restrict__ from the
+// kernels (see the epilogues' note).
+template <typename T, bool S2, bool S1, bool DB, typename S = TileStd>
+DEV void conv_dgrad_glds_tile(const T* DY, const T* WT2D, T* DX,
+                              const T* zero16, const ConvShape& cs) {
   const DgradClass<S2> dc(cs);
   const int M = dc.M, K = dc.K;
   const int KFULL = cs.KH * cs.KW * cs.Cout;
   int tm_, tn_;
   conv_tile_order(cs, tm_, tn_);
-  const int m0 = tm_ * BM;
-  const int n0 = tn_ * BN;
-  const WaveCoord wc;
-  f32x4 acc[FM][FN] = {};
+  const int m0 = tm_ * S::BM;
+  const int n0 = tn_ * S::BN;
+  const WaveCoordT<S> wc;
+  f32x4 acc[S::FM][S::FN] = {};
 
-  // one LDS object per buffer, named statically in the 2x-unrolled k-loop
-  __shared__ alignas(16) T As0[BM * BK], As1[BM * BK];
-  __shared__ alignas(16) T Bs0[BN * BK], Bs1[BN * BK];
-  conv_db_kloop<true>(
+  // one LDS object per buffer, named statically in the 2x-unrolled k-loop;
+  // the single-buffer form never touches the second pair, which then takes
+  // no LDS
+  __shared__ alignas(16) T As0[S::BM * BK], As1[DB ? S::BM * BK : 8];
+  __shared__ alignas(16) T Bs0[S::BN * BK], Bs1[DB ? S::BN * BK : 8];
+  conv_db_kloop<DB>(
       As0, As1, Bs0, Bs1, wc, acc, DY, cs.d_ow.lg, cs.d_cout.lg, WT2D,
       (int64_t)KFULL, cs.Cin, m0, n0, K, zero16,
       // d_hw / d_w hold the per-class (Hc*Wc, Wc) divisors under S2
@@ -765,6 +802,37 @@ __global__ void k_conv_dgrad_db(const T* __restrict__ DY,
         }
       });
   dgrad_store<true>(wc, acc, DX, cs, dc, m0, n0);
+}
+
+template <typename T, bool S2 = false, bool S1 = false>
+__launch_bounds__(THREADS)
+__global__ void k_conv_dgrad_db(const T* __restrict__ DY,
+                                const T* __restrict__ WT2D,
+                                T* __restrict__ DX,
+                                const T* __restrict__ zero16, ConvShape cs) {
+  conv_dgrad_glds_tile<T, S2, S1, true>(DY, WT2D, DX, zero16, cs);
+}
+
+// the 128x128 tile (TileWide, see k_conv_fwd_db_wide) for Cin % 128 == 0, as
+// double buffer (64 KB LDS) and on one buffer pair (32 KB, 3 blocks per CU)
+template <bool S2 = false, bool S1 = false>
+__launch_bounds__(THREADS, 2)
+__global__ void k_conv_dgrad_db_wide(const bf16* __restrict__ DY,
+                                     const bf16* __restrict__ WT2D,
+                                     bf16* __restrict__ DX,
+                                     const bf16* __restrict__ zero16,
+                                     ConvShape cs) {
+  conv_dgrad_glds_tile<bf16, S2, S1, true, TileWide>(DY, WT2D, DX, zero16, cs);
+}
+template <bool S2 = false, bool S1 = false>
+__launch_bounds__(THREADS, 3)
+__global__ void k_conv_dgrad_sb_wide(const bf16* __restrict__ DY,
+                                     const bf16* __restrict__ WT2D,
+                                     bf16* __restrict__ DX,
+                                     const bf16* __restrict__ zero16,
+                                     ConvShape cs) {
+  conv_dgrad_glds_tile<bf16, S2, S1, false, TileWide>(DY, WT2D, DX, zero16,
+                                                      cs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1152,6 +1220,61 @@ static int fwd_db_maxk() {
   return maxk;
 }
 
+// TNN_CONV_WIDE: 0 never takes the 128x128 tile (TileWide), 1 (default)
+// chooses per shape, 2 takes it wherever it is eligible
+static int wide_mode() {
+  static const int mode = env_int("TNN_CONV_WIDE", 1);
+  return mode;
+}
+// A/B switch for the wide kernels' buffering: 0 (default) per shape, 1 always
+// the double buffer, 2 always one buffer pair
+static int wide_buf() {
+  static const int buf = env_int("TNN_CONV_WIDE_BUF", 0);
+  return buf;
+}
+
+// The wide tile is eligible for a bf16 GEMM view [M, N, K] on the DMA-staged
+// route when N % 128 == 0 (no N tail). What auto does with an eligible shape
+// was fixed from the per-shape table in profiles/prof_wrn_conv_wide.md
+// (slowest wide run against fastest 128x64 run); `tiles` counts the 128x128
+// tiles of the whole launch.
+enum class Wide { NO, DB, SB };
+constexpr int WIDE_MIN_TILES = 512;   // smallest grid measured (and ahead)
+constexpr int WIDE_FWD_DB_MINK = 2048;
+constexpr int WIDE_DGRAD_SB_MAXK = 1152;
+static Wide wide_pick(bool eligible, int tiles, bool take, bool single) {
+  if (!eligible || wide_mode() == 0) return Wide::NO;
+  if (wide_mode() == 1 && !(take && tiles >= WIDE_MIN_TILES)) return Wide::NO;
+  if (wide_buf() != 0) single = wide_buf() == 2;
+  return single ? Wide::SB : Wide::DB;
+}
+// forward, K = KH*KW*Cin:
+//   one n-tile (Cout == 128)   one buffer pair wins 8-9 %; not with fused
+//                              statistics, whose atomics then cost more than
+//                              the tile saves (g1: 148 -> 190 us)
+//   more n-tiles               the double buffer wins 11-26 % from K = 2304
+//                              up; below that (K <= 1152) nothing wins
+static Wide fwd_wide(DT dt, bool have_wt2, const ConvShape& cs, bool stats) {
+  const int nt = cs.Cout / TileWide::BN;
+  const int K = cs.KH * cs.KW * cs.Cin;
+  const bool take = nt == 1 ? !stats : K >= WIDE_FWD_DB_MINK;
+  return wide_pick(
+      have_wt2 && dt == DT::BF16 && cs.Cout % TileWide::BN == 0,
+      ceil_div(cs.N * cs.OH * cs.OW, TileWide::BM) * nt, take, nt == 1);
+}
+// dgrad, K = taps * Cout with the taps of one parity class where the route is
+// parity: wide wins or ties on every measured shape (5-43 %), on one buffer
+// pair up to K = 1152 and double-buffered from K = 2048 up
+static Wide dgrad_wide(DT dt, bool have_wt2d, bool s2, const ConvShape& cs) {
+  const int M = s2 ? cs.N * (cs.H / 2) * (cs.W / 2) : cs.N * cs.H * cs.W;
+  const int taps =
+      s2 ? ((cs.KH + 1) / 2) * ((cs.KW + 1) / 2) : cs.KH * cs.KW;
+  return wide_pick(
+      have_wt2d && dt == DT::BF16 && cs.Cin % TileWide::BN == 0,
+      ceil_div(M, TileWide::BM) * (cs.Cin / TileWide::BN) * (s2 ? 4 : 1),
+      true, taps * cs.Cout <= WIDE_DGRAD_SB_MAXK);
+}
+
 template <typename... KArgs, typename... Args>
 static void launch(void (*kern)(KArgs...), dim3 grid, hipStream_t s,
                    Args... args) {
@@ -1203,39 +1326,82 @@ void transpose_w_dgrad_launch(DT dt, const void* w, void* w_t2d, int KHW,
 }
 
 // Route, first match (K = KH*KW*Cin; w_t2 is passed iff conv2d_fwd_wants_db:
-// switch on, all-pow2, vector gate, and for fp32 K <= TNN_DB_MAXK):
+// switch on, all-pow2, vector gate, and for fp32 K <= TNN_DB_MAXK; wide: bf16,
+// Cout % 128 == 0 and TNN_CONV_WIDE says so, see fwd_wide):
+//   w_t2, wide, Cout == 128       k_conv_fwd_sb_wide<stats>
+//   w_t2, wide                    k_conv_fwd_db_wide<stats>
 //   w_t2, bf16, K > TNN_DB_MAXK   k_conv_fwd_sb<stats>
 //   w_t2                          k_conv_fwd_db<T, stats>
 //   all-pow2 and vector gate      k_conv_fwd<T, true, true>    (A by LDS-DMA)
 //   all-pow2                      k_conv_fwd<T, true, false>
 //   otherwise                     k_conv_fwd<T, false, false>
 // stats is honoured on the w_t2 routes only.
+enum class FwdRoute { SB_WIDE, DB_WIDE, SB, DB, GLDS, POW2, GENERIC };
+static FwdRoute fwd_route(DT dt, const void* x, bool have_wt2,
+                          const ConvShape& cs, bool stats) {
+  if (have_wt2) {
+    const Wide wide = fwd_wide(dt, true, cs, stats);
+    if (wide != Wide::NO)
+      return wide == Wide::SB ? FwdRoute::SB_WIDE : FwdRoute::DB_WIDE;
+    const bool long_k =
+        dt == DT::BF16 && cs.KH * cs.KW * cs.Cin > fwd_db_maxk();
+    return long_k ? FwdRoute::SB : FwdRoute::DB;
+  }
+  if (!all_pow2(cs)) return FwdRoute::GENERIC;
+  return vec_ok(dt, x, cs.Cin) ? FwdRoute::GLDS : FwdRoute::POW2;
+}
+
+const char* conv2d_fwd_route(DT dt, const void* x, const ConvShape& cs,
+                             bool stats) {
+  const bool db = conv2d_fwd_wants_db(dt, x, cs);
+  switch (fwd_route(dt, x, db, cs, db && stats)) {
+    case FwdRoute::SB_WIDE: return "k_conv_fwd_sb_wide";
+    case FwdRoute::DB_WIDE: return "k_conv_fwd_db_wide";
+    case FwdRoute::SB: return "k_conv_fwd_sb";
+    case FwdRoute::DB: return "k_conv_fwd_db";
+    case FwdRoute::GLDS: return "k_conv_fwd<pow2, glds>";
+    case FwdRoute::POW2: return "k_conv_fwd<pow2>";
+    default: return "k_conv_fwd";
+  }
+}
+
 void conv2d_fwd_launch(DT dt, const void* x, const void* w, const void* w_t2,
                        const void* bias, void* y, const void* zero16,
                        float* stats, const ConvShape& cs, bool relu,
                        hipStream_t s) {
   int M = cs.N * cs.OH * cs.OW;
   dim3 grid(ceil_div(M, BM), ceil_div(cs.Cout, BN));
+  dim3 grid_wide(ceil_div(M, TileWide::BM), ceil_div(cs.Cout, TileWide::BN));
   int act = relu ? ACT_RELU : ACT_LINEAR;
-  bool p2 = all_pow2(cs);
-  bool g = p2 && vec_ok(dt, x, cs.Cin);
+  const FwdRoute route =
+      fwd_route(dt, x, w_t2 != nullptr, cs, stats != nullptr);
   dispatch_dt(dt, [&](auto tag) {
     using T = typename decltype(tag)::type;
     auto X = (const T*)x;
     auto B = (const T*)bias;
     auto Y = (T*)y;
     auto Z = (const T*)zero16;
-    if (w_t2) {
-      if constexpr (sizeof(T) == 2) {
-        if (cs.KH * cs.KW * cs.Cin > fwd_db_maxk())
-          return launch(stats ? k_conv_fwd_sb<true> : k_conv_fwd_sb<false>,
-                        grid, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
-      }
+    if constexpr (sizeof(T) == 2) {
+      // bf16 only (fwd_route never names these for fp32)
+      if (route == FwdRoute::SB_WIDE)
+        return launch(
+            stats ? k_conv_fwd_sb_wide<true> : k_conv_fwd_sb_wide<false>,
+            grid_wide, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
+      if (route == FwdRoute::DB_WIDE)
+        return launch(
+            stats ? k_conv_fwd_db_wide<true> : k_conv_fwd_db_wide<false>,
+            grid_wide, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
+      if (route == FwdRoute::SB)
+        return launch(stats ? k_conv_fwd_sb<true> : k_conv_fwd_sb<false>,
+                      grid, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
+    }
+    if (route == FwdRoute::DB)
       return launch(stats ? k_conv_fwd_db<T, true> : k_conv_fwd_db<T, false>,
                     grid, s, X, (const T*)w_t2, B, Y, Z, cs, act, stats);
-    }
-    launch(g ? k_conv_fwd<T, true, true>
-             : (p2 ? k_conv_fwd<T, true, false> : k_conv_fwd<T, false, false>),
+    launch(route == FwdRoute::GLDS
+               ? k_conv_fwd<T, true, true>
+               : (route == FwdRoute::POW2 ? k_conv_fwd<T, true, false>
+                                          : k_conv_fwd<T, false, false>),
            grid, s, X, (const T*)w, B, Y, Z, cs, act);
   });
 }
@@ -1248,11 +1414,28 @@ bool conv2d_dgrad_wants_db(DT dt, const void* dy, const ConvShape& cs) {
          vec_ok(dt, dy, cs.Cout);
 }
 
+// the parity route's per-class shape; false where the route does not apply
+static bool dgrad_parity(const ConvShape& cs, ConvShape& cs2) {
+  bool s2 = all_pow2(cs) && cs.SH == 2 && cs.SW == 2 && cs.H % 2 == 0 &&
+            cs.W % 2 == 0;
+  cs2 = cs;
+  if (s2) {
+    cs2.d_hw.set((cs.H / 2) * (cs.W / 2));
+    cs2.d_w.set(cs.W / 2);
+    s2 = cs2.d_hw.lg >= 0 && cs2.d_w.lg >= 0;
+  }
+  return s2;
+}
+
 // Route, first match (w_t2d is passed iff conv2d_dgrad_wants_db: switch on,
 // all-pow2, vector gate, KH*KW*Cout <= TNN_DB_MAXK_DGRAD; else w_t).
 // parity = all-pow2, stride 2x2, even H and W, pow2 per-class divisors: 4
 // classes in grid.z over an M/4-row problem (see DgradClass), cs with the
 // per-class divisors.
+// wide: bf16, Cin % 128 == 0 and TNN_CONV_WIDE says so (dgrad_wide); the wide
+// routes take the same parity / stride-1 / any-stride forms:
+//   w_t2d, wide, K <= 1152        k_conv_dgrad_sb_wide<S2, S1>
+//   w_t2d, wide                   k_conv_dgrad_db_wide<S2, S1>
 //   w_t2d, parity                 k_conv_dgrad_db<T, S2>
 //   w_t2d, stride 1x1             k_conv_dgrad_db<T, -, S1>
 //   w_t2d                         k_conv_dgrad_db<T>           (any stride)
@@ -1261,6 +1444,29 @@ bool conv2d_dgrad_wants_db(DT dt, const void* dy, const ConvShape& cs) {
 //   vector gate                   k_conv_dgrad<T, true, true>
 //   all-pow2                      k_conv_dgrad<T, true, false>
 //   otherwise                     k_conv_dgrad<T, false, false>
+const char* conv2d_dgrad_route(DT dt, const void* dy, const ConvShape& cs) {
+  ConvShape cs2;
+  const bool s2 = dgrad_parity(cs, cs2);
+  const bool s1 = cs.SH == 1 && cs.SW == 1;
+  const bool p2 = all_pow2(cs);
+  if (conv2d_dgrad_wants_db(dt, dy, cs)) {
+    const Wide wide = dgrad_wide(dt, true, s2, cs);
+    if (wide == Wide::SB)
+      return s2 ? "k_conv_dgrad_sb_wide<S2>"
+                : (s1 ? "k_conv_dgrad_sb_wide<S1>" : "k_conv_dgrad_sb_wide");
+    if (wide == Wide::DB)
+      return s2 ? "k_conv_dgrad_db_wide<S2>"
+                : (s1 ? "k_conv_dgrad_db_wide<S1>" : "k_conv_dgrad_db_wide");
+    return s2 ? "k_conv_dgrad_db<S2>"
+              : (s1 ? "k_conv_dgrad_db<S1>" : "k_conv_dgrad_db");
+  }
+  if (p2 && vec_ok(dt, dy, cs.Cout))
+    return s2 ? "k_conv_dgrad<pow2, glds, S2>"
+              : (s1 ? "k_conv_dgrad<pow2, glds, S1>"
+                    : "k_conv_dgrad<pow2, glds>");
+  return p2 ? "k_conv_dgrad<pow2>" : "k_conv_dgrad";
+}
+
 void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
                          const void* w_t2d, void* dx, const void* zero16,
                          const ConvShape& cs, hipStream_t s) {
@@ -1269,20 +1475,35 @@ void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
   bool p2 = all_pow2(cs);
   bool g = p2 && vec_ok(dt, dy, cs.Cout);
   bool s1 = cs.SH == 1 && cs.SW == 1;
-  bool s2 = p2 && cs.SH == 2 && cs.SW == 2 && cs.H % 2 == 0 && cs.W % 2 == 0;
-  ConvShape cs2 = cs;
-  if (s2) {
-    cs2.d_hw.set((cs.H / 2) * (cs.W / 2));
-    cs2.d_w.set(cs.W / 2);
-    s2 = cs2.d_hw.lg >= 0 && cs2.d_w.lg >= 0;
-  }
-  dim3 grid_s2(ceil_div(cs.N * (cs.H / 2) * (cs.W / 2), BM),
-               ceil_div(cs.Cin, BN), 4);
+  ConvShape cs2;
+  bool s2 = dgrad_parity(cs, cs2);
+  int Mc = cs.N * (cs.H / 2) * (cs.W / 2);   // rows of one parity class
+  dim3 grid_s2(ceil_div(Mc, BM), ceil_div(cs.Cin, BN), 4);
+  const Wide wide = dgrad_wide(dt, w_t2d != nullptr, s2, cs);
   dispatch_dt(dt, [&](auto tag) {
     using T = typename decltype(tag)::type;
     auto DY = (const T*)dy;
     auto DX = (T*)dx;
     auto Z = (const T*)zero16;
+    if constexpr (sizeof(T) == 2) {
+      if (wide != Wide::NO) {   // bf16 only
+        auto WT = (const T*)w_t2d;
+        constexpr int WBM = TileWide::BM, WBN = TileWide::BN;
+        const bool sb = wide == Wide::SB;
+        if (s2)
+          return launch(sb ? k_conv_dgrad_sb_wide<true>
+                           : k_conv_dgrad_db_wide<true>,
+                        dim3(ceil_div(Mc, WBM), cs.Cin / WBN, 4), s, DY, WT,
+                        DX, Z, cs2);
+        dim3 gw(ceil_div(M, WBM), cs.Cin / WBN);
+        if (s1)
+          return launch(sb ? k_conv_dgrad_sb_wide<false, true>
+                           : k_conv_dgrad_db_wide<false, true>,
+                        gw, s, DY, WT, DX, Z, cs);
+        return launch(sb ? k_conv_dgrad_sb_wide<> : k_conv_dgrad_db_wide<>,
+                      gw, s, DY, WT, DX, Z, cs);
+      }
+    }
     if (w_t2d) {
       auto WT = (const T*)w_t2d;
       if (s2)

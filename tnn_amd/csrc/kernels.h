@@ -150,6 +150,11 @@ void conv2d_fwd_launch(DT dt, const void* x, const void* w, const void* w_t2,
                        float* stats, const ConvShape& cs, bool relu,
                        hipStream_t s);
 bool conv2d_dgrad_wants_db(DT dt, const void* dy, const ConvShape& cs);
+// name of the kernel the launch below takes for this shape (given the weight
+// layout the matching wants_db asks for; stats: fused statistics wanted)
+const char* conv2d_fwd_route(DT dt, const void* x, const ConvShape& cs,
+                             bool stats);
+const char* conv2d_dgrad_route(DT dt, const void* dy, const ConvShape& cs);
 void transpose_w_dgrad_launch(DT dt, const void* w, void* w_t2d, int KHW,
                               int Cin, int Cout, hipStream_t s);
 void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,

@@ -17,18 +17,40 @@
 //   - bf16: v_mfma_f32_16x16x32_bf16; fp32: v_mfma_f32_16x16x4_f32
 //     (exact f32 at the f32 vector rate — no xf32 on gfx950).
 //   - Each wave owns a 64x32 sub-tile: 4x2 fragments, f32x4 accumulators.
+//   - The block tile is a compile-time shape tag (TileShape). Everything
+//     defaults to the geometry above; the bf16 DMA-staged conv kernels also
+//     come in TileWide, 128x128 with 64x64 wave tiles (4x4 fragments), which
+//     stages two thirds of the bytes per FLOP. Both shapes share BK, the
+//     swizzled [rows][BK] image and the per-element MFMA sequence.
 #pragma once
 
 #include "common.h"
 
 namespace tile {
 
-constexpr int BM = 128, BN = 64, BK = 64, THREADS = 256;
-constexpr int WAVES_M = 2, WAVES_N = 2;      // wave grid
-constexpr int WM = BM / WAVES_M;             // 64 rows per wave
-constexpr int WN = BN / WAVES_N;             // 32 cols per wave
-constexpr int FM = WM / 16;                  // 4 row fragments
-constexpr int FN = WN / 16;                  // 2 col fragments
+constexpr int BK = 64, THREADS = 256;
+
+template <int BM_, int BN_, int WAVES_M_ = 2, int WAVES_N_ = 2>
+struct TileShape {
+  static constexpr int BM = BM_, BN = BN_;
+  static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_;  // wave grid
+  static constexpr int WM = BM / WAVES_M;      // rows per wave
+  static constexpr int WN = BN / WAVES_N;      // cols per wave
+  static constexpr int FM = WM / 16;           // row fragments
+  static constexpr int FN = WN / 16;           // col fragments
+  static_assert(WAVES_M * WAVES_N * 64 == THREADS, "one wave per sub-tile");
+  static_assert(WM % 16 == 0 && WN % 16 == 0, "whole 16x16 fragments");
+};
+using TileStd = TileShape<128, 64>;     // 64x32 wave tiles, 4x2 fragments
+using TileWide = TileShape<128, 128>;   // 64x64 wave tiles, 4x4 fragments
+
+// the default shape's numbers, for everything that does not take a tag
+constexpr int BM = TileStd::BM, BN = TileStd::BN;
+constexpr int WAVES_M = TileStd::WAVES_M, WAVES_N = TileStd::WAVES_N;
+constexpr int WM = TileStd::WM;              // 64 rows per wave
+constexpr int WN = TileStd::WN;              // 32 cols per wave
+constexpr int FM = TileStd::FM;              // 4 row fragments
+constexpr int FN = TileStd::FN;              // 2 col fragments
 
 // 16-byte staging pack (dwordx4 load/store); ext_vector_type cannot hold
 // the __hip_bfloat16 struct, an aligned POD array can.
@@ -116,15 +138,18 @@ DEV void tile_remap_xcd(int& tm, int& tn) {
   tn = rem / gm;
 }
 
-struct WaveCoord {
+template <typename S = TileStd>
+struct WaveCoordT {
+  using Shape = S;
   int wid, lane, wrow0, wcol0;
-  DEV WaveCoord() {
+  DEV WaveCoordT() {
     wid = threadIdx.x >> 6;
     lane = threadIdx.x & 63;
-    wrow0 = (wid / WAVES_N) * WM;
-    wcol0 = (wid % WAVES_N) * WN;
+    wrow0 = (wid / S::WAVES_N) * S::WM;
+    wcol0 = (wid % S::WAVES_N) * S::WN;
   }
 };
+using WaveCoord = WaveCoordT<>;
 
 // ---- async global->LDS staging for the A tile (gfx950 global_load_lds) ---
 // Writes the whole [BM][BK] swizzled image with 16B-per-lane DMA: each
@@ -265,18 +290,28 @@ DEV RmFrag rm_frag_issue(const bf16* img, int row0, int k0, int lane) {
 
 // lgkmcnt(0) for the fragments of one k-step; the "+v" operands tie every
 // fragment to the wait, so no MFMA that consumes one is scheduled above it
-DEV void rm_frags_wait(RmFrag (&a)[FM], RmFrag (&b)[FN]) {
-  static_assert(FM == 4 && FN == 2, "operand list below");
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(a[0].v), "+v"(a[1].v), "+v"(a[2].v), "+v"(a[3].v),
-                 "+v"(b[0].v), "+v"(b[1].v)
-               :: "memory");
+template <int NFM, int NFN>
+DEV void rm_frags_wait(RmFrag (&a)[NFM], RmFrag (&b)[NFN]) {
+  static_assert(NFM == 4 && (NFN == 2 || NFN == 4), "operand lists below");
+  if constexpr (NFN == 2)
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a[0].v), "+v"(a[1].v), "+v"(a[2].v), "+v"(a[3].v),
+                   "+v"(b[0].v), "+v"(b[1].v)
+                 :: "memory");
+  else
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a[0].v), "+v"(a[1].v), "+v"(a[2].v), "+v"(a[3].v),
+                   "+v"(b[0].v), "+v"(b[1].v), "+v"(b[2].v), "+v"(b[3].v)
+                 :: "memory");
 }
 
 // acc += A_tile * B_tile^T-stored: chunk order, k-steps and MFMA sequence of
 // mfma_compute_tile(bf16), so the accumulators come out bitwise the same
+template <typename S>
 DEV void mfma_compute_tile_nofence(const bf16* As, const bf16* Bs,
-                                   const WaveCoord& w, f32x4 acc[FM][FN]) {
+                                   const WaveCoordT<S>& w,
+                                   f32x4 acc[S::FM][S::FN]) {
+  constexpr int FM = S::FM, FN = S::FN;
 #pragma unroll
   for (int ks = 0; ks < BK / 32; ++ks) {
     RmFrag a[FM], b[FN];
@@ -462,9 +497,10 @@ DEV float colsum_tile_finish(float s) {
 
 // ---- epilogue: C/D fragment map col=lane&15, row=(lane>>4)*4+j ------------
 // Visits every accumulator element with its global (row, col).
-template <typename F>
-DEV void epilogue_visit(const WaveCoord& w, f32x4 acc[FM][FN],
+template <typename S, typename F>
+DEV void epilogue_visit(const WaveCoordT<S>& w, f32x4 acc[S::FM][S::FN],
                         int row0, int col0, F&& emit) {
+  constexpr int FM = S::FM, FN = S::FN;
   const int cr = (w.lane >> 4) * 4;
   const int cc = w.lane & 15;
 #pragma unroll
