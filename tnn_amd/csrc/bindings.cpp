@@ -552,6 +552,18 @@ std::string conv2d_dgrad_route_name(const at::Tensor& dy,
   return conv2d_dgrad_route(dt_of(dy), dy.data_ptr(), cs);
 }
 
+// kernel name and split-M count of conv2d_wgrad / conv2d_wgrad_bias for these
+// arguments (the same with and without the bias row)
+std::tuple<std::string, int64_t> conv2d_wgrad_route_name(
+    const at::Tensor& x, const at::Tensor& dy, int64_t KH, int64_t KW,
+    int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  CHECK_IN(x);
+  CHECK_IN(dy);
+  auto cs = conv_shape(x, x.size(3), dy.size(3), KH, KW, sh, sw, ph, pw);
+  return {conv2d_wgrad_route(dt_of(x), x.data_ptr(), dy.data_ptr(), cs),
+          conv2d_wgrad_zsplits(dt_of(x), x.data_ptr(), dy.data_ptr(), cs)};
+}
+
 // returns [KH*KW*Cin (+1 with bias), Cout]: dw rows, then the bias-gradient row
 static at::Tensor conv2d_wgrad_rows(const at::Tensor& x, const at::Tensor& dy,
                                     int64_t KH, int64_t KW, int64_t sh,
@@ -566,7 +578,7 @@ static at::Tensor conv2d_wgrad_rows(const at::Tensor& x, const at::Tensor& dy,
   auto out = at::empty({rows, (int64_t)cs.Cout},
                        out_dt == DT::F32 ? x.options().dtype(at::kFloat)
                                          : x.options());
-  int z = conv2d_wgrad_zsplits(cs);
+  int z = conv2d_wgrad_zsplits(dt_of(x), x.data_ptr(), dy.data_ptr(), cs);
   at::Tensor ws;
   float* wsp = nullptr;
   if (z > 1 || out_dt != DT::F32) {
@@ -1527,6 +1539,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_dgrad", &tnn::conv2d_dgrad);
   m.def("conv2d_fwd_route", &tnn::conv2d_fwd_route_name);
   m.def("conv2d_dgrad_route", &tnn::conv2d_dgrad_route_name);
+  m.def("conv2d_wgrad_route", &tnn::conv2d_wgrad_route_name);
   m.def("conv2d_wgrad", &tnn::conv2d_wgrad);
   m.def("conv2d_wgrad_bias", &tnn::conv2d_wgrad_bias);
   m.def("bn_fwd_train", &tnn::bn_fwd_train, py::arg("x"), py::arg("gamma"),

@@ -314,14 +314,33 @@ DEV void dgrad_store(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN], T* DX,
 
 // wgrad: block z's tile into slab z of the [z][Kout + bias_row][Cout] fp32
 // workspace; returns the slab
-DEV float* wgrad_slab_store(const WaveCoord& wc, f32x4 acc[FM][FN],
-                            float* DW, const ConvShape& cs, int Kout,
-                            int bias_row, int r0, int n0) {
+template <typename S>
+DEV float* wgrad_slab_store(const WaveCoordT<S>& wc,
+                            f32x4 acc[S::FM][S::FN], float* DW,
+                            const ConvShape& cs, int Kout, int bias_row,
+                            int r0, int n0) {
   float* out = DW + (int64_t)blockIdx.z * (Kout + bias_row) * cs.Cout;
   epilogue_visit(wc, acc, r0, n0, [&](int row, int col, float v) {
     if (row < Kout && col < cs.Cout) out[(int64_t)row * cs.Cout + col] = v;
   });
   return out;
+}
+// bias gradient of the transposed-read kernels: wave (wm, wn) of a tile-row-0
+// block summed fragment columns wcol0 + 16 * (NBF * wm + t) with all-ones
+// MFMAs; every row of bacc[t] is the column sum and lanes 0-15 hold row 0
+template <typename S>
+DEV void wgrad_biasrow_store(float* out, const WaveCoordT<S>& wc,
+                             const f32x4 (&bacc)[S::FN / S::WAVES_M],
+                             const ConvShape& cs, int Kout, int n0) {
+  constexpr int NBF = S::FN / S::WAVES_M;
+  const int wm = wc.wid / S::WAVES_N;
+  if (wc.lane < 16) {
+#pragma unroll
+    for (int t = 0; t < NBF; ++t) {
+      int col = n0 + wc.wcol0 + 16 * (NBF * wm + t) + wc.lane;
+      if (col < cs.Cout) out[(int64_t)Kout * cs.Cout + col] = bacc[t][0];
+    }
+  }
 }
 // bias gradient of the register-staged kernels: the per-thread dy column
 // partials bsum of a tile-row-0 block, folded into row Kout of its slab
@@ -1003,34 +1022,44 @@ __global__ void k_conv_wgrad_vec(const T* __restrict__ X,
 // Same gate as k_conv_wgrad_vec: all-pow2 shape, Cin%8 == Cout%8 == 0,
 // 16B-aligned tensors. Double-buffered k-loop (48 KB LDS, 3 blocks/CU): it
 // measured 3-5% ahead of the single-buffer form (24 KB) on the WRN shapes.
+//
+// One body for both block tiles (S) and both bufferings (DB; As1 / Bs1 are
+// unused on one buffer pair). The A image is [BK][S::BM] with S::BM == 128;
+// B is [BK][S::BN], 8 or 16 chunks per k-row. Chunk order, k-steps and the
+// MFMA sequence per output element do not depend on S or DB, so dw and db
+// are bitwise the same on every form for the same split count.
 // ---------------------------------------------------------------------------
-__launch_bounds__(THREADS, 2)  // <=256 regs: MFMA accumulators stay in VGPRs
-__global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
-                                const bf16* __restrict__ DY,
-                                float* __restrict__ DW,
-                                const bf16* __restrict__ zero16, ConvShape cs,
-                                int bias_row) {
-  constexpr int NA = glds_kmajor_count<BM / 8>();   // A glds per wave (4)
-  constexpr int NPER = NA + glds_kmajor_count<BN / 8>();
-  // one LDS object per buffer, named statically in the 2x-unrolled k-loop
-  __shared__ alignas(16) bf16 As0[BK * BM], As1[BK * BM];  // [m][(kh,kw,ci)]
-  __shared__ alignas(16) bf16 Bs0[BK * BN], Bs1[BK * BN];  // [m][co]
+template <bool DB, typename S>
+DEV void conv_wgrad_tr_tile(bf16* As0, bf16* As1, bf16* Bs0, bf16* Bs1,
+                            const bf16* __restrict__ X,
+                            const bf16* __restrict__ DY,
+                            float* __restrict__ DW,
+                            const bf16* __restrict__ zero16,
+                            const ConvShape& cs, int bias_row) {
+  constexpr int FM = S::FM, FN = S::FN;
+  constexpr int ACH = S::BM / 8, BCH = S::BN / 8;   // 16-byte chunks per k-row
+  static_assert(ACH == 16, "the hoisted A decode below is for 128-row tiles");
+  static_assert(S::WAVES_M == 2, "bias row: wm selects half the fragments");
+  constexpr int NA = glds_kmajor_count<ACH>();   // A glds per wave (4)
+  constexpr int NPER = NA + glds_kmajor_count<BCH>();
+  constexpr int NBF = FN / S::WAVES_M;   // bias-row fragments per wave
   const int M = cs.N * cs.OH * cs.OW;
   const int Kout = cs.KH * cs.KW * cs.Cin;
   int tr_, tn_;
   conv_tile_order(cs, tr_, tn_);
-  const int r0 = tr_ * BM;
-  const int n0 = tn_ * BN;
+  const int r0 = tr_ * S::BM;
+  const int n0 = tn_ * S::BN;
   const int m_begin = (int)((int64_t)M * blockIdx.z / gridDim.z);
   const int m_end = (int)((int64_t)M * (blockIdx.z + 1) / gridDim.z);
-  const WaveCoord wc;
-  const int wm = wc.wid / WAVES_N;
+  const WaveCoordT<S> wc;
+  const int wm = wc.wid / S::WAVES_N;
   f32x4 acc[FM][FN] = {};
   // bias gradient (see k_conv_wgrad): the dy fragments are already in
-  // registers, so tile-row 0 sums them with one all-ones MFMA per k-step;
-  // wave (wm, wn) takes the 16 columns wcol0 + 16*wm
+  // registers, so tile-row 0 sums them with all-ones MFMAs, one per k-step
+  // and fragment; wave (wm, wn) takes the NBF fragments from column
+  // wcol0 + 16*NBF*wm on, half of its wave tile
   const bool colsum = bias_row && tr_ == 0;
-  f32x4 bacc = {};
+  f32x4 bacc[NBF] = {};
   bf16x8 ones;
 #pragma unroll
   for (int j = 0; j < 8; ++j) ones[j] = (__bf16)1.0f;
@@ -1049,8 +1078,8 @@ __global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
   }
 
   auto stage = [&](int k0, bf16* a_img, bf16* b_img) {
-    glds_stage_kmajor<BM / 8>(a_img, wc,
-                              [&](int i, int row, int) -> const bf16* {
+    glds_stage_kmajor<ACH>(a_img, wc,
+                           [&](int i, int row, int) -> const bf16* {
       // branch-free: an invalid lane's address is computed but never used
       const int gm = k0 + row;
       const int n = gm >> cs.d_ohow.lg;
@@ -1066,8 +1095,8 @@ __global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
       const bf16* p = X + (((int64_t)pix << cs.d_cin.lg) + a_ci[i]);
       return ok ? p : zero16;
     });
-    glds_stage_kmajor<BN / 8>(b_img, wc,
-                              [&](int, int row, int ch) -> const bf16* {
+    glds_stage_kmajor<BCH>(b_img, wc,
+                           [&](int, int row, int ch) -> const bf16* {
       const int gm = k0 + row, gn = n0 + 8 * ch;
       const bf16* p = DY + (((int64_t)gm << cs.d_cout.lg) + gn);
       return gm < m_end && gn < cs.Cout ? p : zero16;
@@ -1079,22 +1108,25 @@ __global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
       TrFrag a[FM], b[FN];
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm)
-        a[fm] = tr_frag_issue<BM / 8>(a_img, ks * 32, wc.wrow0 + fm * 16,
-                                      wc.lane);
+        a[fm] = tr_frag_issue<ACH>(a_img, ks * 32, wc.wrow0 + fm * 16,
+                                   wc.lane);
 #pragma unroll
       for (int fn = 0; fn < FN; ++fn)
-        b[fn] = tr_frag_issue<BN / 8>(b_img, ks * 32, wc.wcol0 + fn * 16,
-                                      wc.lane);
-      tr_frags_wait(a, b);
+        b[fn] = tr_frag_issue<BCH>(b_img, ks * 32, wc.wcol0 + fn * 16,
+                                   wc.lane);
+      tr_frags_wait<S>(a, b);
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
         for (int fn = 0; fn < FN; ++fn)
           acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               a[fm].get(), b[fn].get(), acc[fm][fn], 0, 0, 0);
-      if (colsum)
-        bacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            ones, wm ? b[1].get() : b[0].get(), bacc, 0, 0, 0);
+      if (colsum) {
+#pragma unroll
+        for (int t = 0; t < NBF; ++t)
+          bacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              ones, wm ? b[NBF + t].get() : b[t].get(), bacc[t], 0, 0, 0);
+      }
     }
   };
 
@@ -1112,17 +1144,64 @@ __global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
     compute(a_cur, b_cur);
     __builtin_amdgcn_s_barrier();   // cur free for the chunk after next
   };
-  if (m_begin < m_end) stage(m_begin, As0, Bs0);
-  for (int k0 = m_begin; k0 < m_end; k0 += 2 * BK) {
-    step(k0, As0, Bs0, As1, Bs1);
-    if (k0 + BK < m_end) step(k0 + BK, As1, Bs1, As0, Bs0);
+  if constexpr (DB) {
+    if (m_begin < m_end) stage(m_begin, As0, Bs0);
+    for (int k0 = m_begin; k0 < m_end; k0 += 2 * BK) {
+      step(k0, As0, Bs0, As1, Bs1);
+      if (k0 + BK < m_end) step(k0 + BK, As1, Bs1, As0, Bs0);
+    }
+  } else {
+    // one buffer pair: half the LDS, one more resident block, no overlap
+    // inside a block
+    for (int k0 = m_begin; k0 < m_end; k0 += BK) {
+      stage(k0, As0, Bs0);
+      wait_vmcnt<0>();
+      __builtin_amdgcn_s_barrier();
+      compute(As0, Bs0);
+      __builtin_amdgcn_s_barrier();
+    }
   }
 
   float* out = wgrad_slab_store(wc, acc, DW, cs, Kout, bias_row, r0, n0);
-  if (colsum && wc.lane < 16) {
-    // every row of bacc is the column sum; lanes 0-15 hold row 0
-    int col = n0 + wc.wcol0 + 16 * wm + wc.lane;
-    if (col < cs.Cout) out[(int64_t)Kout * cs.Cout + col] = bacc[0];
+  if (colsum) wgrad_biasrow_store<S>(out, wc, bacc, cs, Kout, n0);
+}
+
+__launch_bounds__(THREADS, 2)  // <=256 regs: MFMA accumulators stay in VGPRs
+__global__ void k_conv_wgrad_tr(const bf16* __restrict__ X,
+                                const bf16* __restrict__ DY,
+                                float* __restrict__ DW,
+                                const bf16* __restrict__ zero16, ConvShape cs,
+                                int bias_row) {
+  // one LDS object per buffer, named statically in the 2x-unrolled k-loop
+  __shared__ alignas(16) bf16 As0[BK * BM], As1[BK * BM];  // [m][(kh,kw,ci)]
+  __shared__ alignas(16) bf16 Bs0[BK * BN], Bs1[BK * BN];  // [m][co]
+  conv_wgrad_tr_tile<true, TileStd>(As0, As1, Bs0, Bs1, X, DY, DW, zero16, cs,
+                                    bias_row);
+}
+
+// the 128x128 tile (TileWide) of k_conv_wgrad_tr for Cout % 128 == 0: one
+// transposed read per MFMA where the 128x64 tile issues 1.5, 32 KB of images
+// per 2.1 MFLOP chunk instead of 24 KB per 1.05, and the gathered-x image
+// with its (n, oh, ow) decode is fetched once per 128 output channels. The B
+// image takes the 16-chunk layout A has. DB: 64 KB LDS, 2 blocks per CU;
+// one buffer pair: 32 KB, capped at the 168 registers of 3 waves per SIMD.
+template <bool DB>
+__launch_bounds__(THREADS, DB ? 2 : 3)
+__global__ void k_conv_wgrad_tr_wide(const bf16* __restrict__ X,
+                                     const bf16* __restrict__ DY,
+                                     float* __restrict__ DW,
+                                     const bf16* __restrict__ zero16,
+                                     ConvShape cs, int bias_row) {
+  constexpr int WBM = TileWide::BM, WBN = TileWide::BN;
+  if constexpr (DB) {
+    __shared__ alignas(16) bf16 As0[BK * WBM], As1[BK * WBM];
+    __shared__ alignas(16) bf16 Bs0[BK * WBN], Bs1[BK * WBN];
+    conv_wgrad_tr_tile<true, TileWide>(As0, As1, Bs0, Bs1, X, DY, DW, zero16,
+                                       cs, bias_row);
+  } else {
+    __shared__ alignas(16) bf16 As0[BK * WBM], Bs0[BK * WBN];
+    conv_wgrad_tr_tile<false, TileWide>(As0, As0, Bs0, Bs0, X, DY, DW, zero16,
+                                        cs, bias_row);
   }
 }
 
@@ -1524,23 +1603,134 @@ void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
   });
 }
 
-int conv2d_wgrad_zsplits(const ConvShape& cs) {
-  int M = cs.N * cs.OH * cs.OW;
-  int Kout = cs.KH * cs.KW * cs.Cin;
-  int base = ceil_div(Kout, BM) * ceil_div(cs.Cout, BN);
-  int want = 2048;
-  int z = base >= want ? 1
-                       : std::min(ceil_div(M, 4 * BK), ceil_div(want, base));
-  return std::max(z, 1);
+// TNN_WGRAD_WIDE: 0 never takes the 128x128 tile for wgrad, 1 (default)
+// chooses per shape, 2 takes it wherever it is eligible. TNN_WGRAD_WIDE_BUF:
+// 0 (default) per shape, 1 always the double buffer, 2 always one buffer
+// pair. Separate from TNN_CONV_WIDE, which keeps steering fwd and dgrad only.
+static int wgrad_wide_mode() {
+  static const int mode = env_int("TNN_WGRAD_WIDE", 1);
+  return mode;
+}
+static int wgrad_wide_buf() {
+  static const int buf = env_int("TNN_WGRAD_WIDE_BUF", 0);
+  return buf;
+}
+// TNN_WGRAD_SPLITS=<z> pins the split count of every wgrad launch (clamped to
+// [1, ceil(M / (4*BK))]); 0 or unset leaves it to the policy below
+static int wgrad_splits_pin() {
+  static const int z = env_int("TNN_WGRAD_SPLITS", 0);
+  return z;
 }
 
 // Route, first match (vector gate: all-pow2, Cin and Cout multiples of the
-// vector width, x and dy 16-byte aligned):
+// vector width, x and dy 16-byte aligned; wide: Cout % 128 == 0 and
+// TNN_WGRAD_WIDE says so, see wgrad_wide):
+//   vector gate, bf16, wide       k_conv_wgrad_tr_wide<db> or <sb>
 //   vector gate, bf16             k_conv_wgrad_tr
 //   vector gate, fp32             k_conv_wgrad_vec<float>
 //   all-pow2                      k_conv_wgrad<T, true>
 //   otherwise                     k_conv_wgrad<T, false>
-// then the split-M reduce unless the kernel wrote dw_out directly.
+// then the split-M reduce unless the kernel wrote dw_out directly. The route
+// is a function of the shape, dtype and alignment only -- never of whether
+// the bias row is asked for.
+enum class WgradRoute { TR_WIDE_DB, TR_WIDE_SB, TR, VEC, POW2, GENERIC };
+
+// What auto does with an eligible shape, from the per-shape table in
+// profiles/prof_wrn_wgrad_wide.md (slowest wide timing against the fastest
+// 128x64 timing, reduce included), `tiles` = 128x128 tiles of dw:
+// in time saved:
+//   grid size                   one resident wave ties or beats two on every
+//                               shape and form (up to 30 %); two beat four
+//   Cout == 128, Kout = 1152    (g1) both forms lose 2-12 % at every grid
+//                               size: stays on k_conv_wgrad_tr
+//   Cout == 128, Kout <= 144    (16->128 entry and 1x1) double buffer 28-31 %,
+//                               one buffer pair 15-19 %
+//   Cout >= 256, tiles <= 72    double buffer 4-21 %, one buffer pair 2-16 %
+//   tiles = 144                 (g3) one buffer pair 8 %, the double buffer
+//                               5 % (its 3 splits fill 432 of 512 slots)
+// Shapes whose split cap leaves less than one resident wave of wide blocks
+// were not measured and stay on the 128x64 tile, which makes more blocks.
+constexpr int WGRAD_WIDE_WAVES = 1;
+constexpr int WGRAD_WIDE_1TILE_MAXKOUT = 144;
+constexpr int WGRAD_WIDE_SB_MINTILES = 144;
+constexpr int WGRAD_WIDE_DB_SLOTS = 512, WGRAD_WIDE_SB_SLOTS = 768;
+// TNN_WGRAD_WAVES=<n> sizes the wide grids to n resident waves (the sweep)
+static int wgrad_wide_waves() {
+  static const int n =
+      std::max(env_int("TNN_WGRAD_WAVES", WGRAD_WIDE_WAVES), 1);
+  return n;
+}
+static Wide wgrad_wide_auto(const ConvShape& cs) {
+  const int Kout = cs.KH * cs.KW * cs.Cin;
+  const int nt = cs.Cout / TileWide::BN;
+  const int tiles = ceil_div(Kout, TileWide::BM) * nt;
+  const int cap = ceil_div(cs.N * cs.OH * cs.OW, 4 * BK);
+  if (nt == 1 && Kout > WGRAD_WIDE_1TILE_MAXKOUT) return Wide::NO;
+  if (cap < WGRAD_WIDE_DB_SLOTS / tiles) return Wide::NO;
+  return tiles >= WGRAD_WIDE_SB_MINTILES ? Wide::SB : Wide::DB;
+}
+static Wide wgrad_wide(const ConvShape& cs) {
+  if (cs.Cout % TileWide::BN != 0 || wgrad_wide_mode() == 0) return Wide::NO;
+  Wide pick = wgrad_wide_auto(cs);
+  if (wgrad_wide_mode() == 1 && pick == Wide::NO) return Wide::NO;
+  if (wgrad_wide_buf() != 0)
+    pick = wgrad_wide_buf() == 2 ? Wide::SB : Wide::DB;
+  else if (pick == Wide::NO)
+    pick = Wide::DB;   // forced (mode 2) where auto would not go wide
+  return pick;
+}
+
+static WgradRoute wgrad_route(DT dt, const void* x, const void* dy,
+                              const ConvShape& cs) {
+  const bool p2 = all_pow2(cs);
+  if (p2 && vec_ok(dt, x, cs.Cin) && vec_ok(dt, dy, cs.Cout)) {
+    if (dt != DT::BF16) return WgradRoute::VEC;
+    const Wide wide = wgrad_wide(cs);
+    if (wide == Wide::NO) return WgradRoute::TR;
+    return wide == Wide::SB ? WgradRoute::TR_WIDE_SB : WgradRoute::TR_WIDE_DB;
+  }
+  return p2 ? WgradRoute::POW2 : WgradRoute::GENERIC;
+}
+
+// Split-M count of the launch wgrad_route names; the bindings size the slab
+// workspace from it. 128x64 kernels: about 2048 blocks. Wide kernels: the
+// grid is sized to the resident slots of their form (256 CUs x 2 blocks
+// double-buffered, x 3 on one buffer pair) times WGRAD_WIDE_WAVES, rounded
+// down -- every block writes its whole fp32 tile to a slab, so slab bytes are
+// blocks x tile bytes, and 2048 blocks of 64 KB would double them.
+int conv2d_wgrad_zsplits(DT dt, const void* x, const void* dy,
+                         const ConvShape& cs) {
+  const int M = cs.N * cs.OH * cs.OW;
+  const int Kout = cs.KH * cs.KW * cs.Cin;
+  const int cap = std::max(ceil_div(M, 4 * BK), 1);
+  if (wgrad_splits_pin() > 0) return std::min(wgrad_splits_pin(), cap);
+  const WgradRoute route = wgrad_route(dt, x, dy, cs);
+  if (route == WgradRoute::TR_WIDE_DB || route == WgradRoute::TR_WIDE_SB) {
+    const int base = ceil_div(Kout, TileWide::BM) * (cs.Cout / TileWide::BN);
+    const int slots = (route == WgradRoute::TR_WIDE_DB ? WGRAD_WIDE_DB_SLOTS
+                                                       : WGRAD_WIDE_SB_SLOTS) *
+                      wgrad_wide_waves();
+    return std::max(std::min(cap, slots / base), 1);
+  }
+  int base = ceil_div(Kout, BM) * ceil_div(cs.Cout, BN);
+  int want = 2048;
+  int z = base >= want ? 1 : std::min(cap, ceil_div(want, base));
+  return std::max(z, 1);
+}
+
+const char* conv2d_wgrad_route(DT dt, const void* x, const void* dy,
+                               const ConvShape& cs) {
+  switch (wgrad_route(dt, x, dy, cs)) {
+    case WgradRoute::TR_WIDE_DB: return "k_conv_wgrad_tr_wide<db>";
+    case WgradRoute::TR_WIDE_SB: return "k_conv_wgrad_tr_wide<sb>";
+    case WgradRoute::TR: return "k_conv_wgrad_tr";
+    case WgradRoute::VEC: return "k_conv_wgrad_vec";
+    case WgradRoute::POW2: return "k_conv_wgrad<pow2>";
+    default: return "k_conv_wgrad";
+  }
+}
+
+// z: conv2d_wgrad_zsplits of the same arguments (the workspace holds z slabs)
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
                          const ConvShape& cs, bool bias, hipStream_t s) {
@@ -1553,22 +1743,32 @@ void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
   bool direct = z == 1 && out_dt == DT::F32;
   float* target = direct ? (float*)dw_out : ws;
   dim3 grid(ceil_div(Kout, BM), ceil_div(cs.Cout, BN), z);
-  bool p2 = all_pow2(cs);
-  bool vec = p2 && vec_ok(dt, x, cs.Cin) && vec_ok(dt, dy, cs.Cout);
+  const WgradRoute route = wgrad_route(dt, x, dy, cs);
   dispatch_dt(dt, [&](auto tag) {
     using T = typename decltype(tag)::type;
     auto X = (const T*)x;
     auto DY = (const T*)dy;
     auto Z = (const T*)zero16;
-    if (vec) {
-      if constexpr (sizeof(T) == 2)
-        launch(k_conv_wgrad_tr, grid, s, X, DY, target, Z, cs, bias_row);
-      else
-        launch(k_conv_wgrad_vec<T>, grid, s, X, DY, target, Z, cs, bias_row);
-      return;
+    if constexpr (sizeof(T) == 2) {
+      // bf16 only (wgrad_route never names these for fp32)
+      if (route == WgradRoute::TR_WIDE_DB || route == WgradRoute::TR_WIDE_SB)
+        return launch(route == WgradRoute::TR_WIDE_DB
+                          ? k_conv_wgrad_tr_wide<true>
+                          : k_conv_wgrad_tr_wide<false>,
+                      dim3(ceil_div(Kout, TileWide::BM),
+                           cs.Cout / TileWide::BN, z),
+                      s, X, DY, target, Z, cs, bias_row);
+      if (route == WgradRoute::TR)
+        return launch(k_conv_wgrad_tr, grid, s, X, DY, target, Z, cs,
+                      bias_row);
+    } else {
+      if (route == WgradRoute::VEC)
+        return launch(k_conv_wgrad_vec<T>, grid, s, X, DY, target, Z, cs,
+                      bias_row);
     }
-    launch(p2 ? k_conv_wgrad<T, true> : k_conv_wgrad<T, false>, grid, s, X,
-           DY, target, cs, bias_row);
+    launch(route == WgradRoute::POW2 ? k_conv_wgrad<T, true>
+                                     : k_conv_wgrad<T, false>,
+           grid, s, X, DY, target, cs, bias_row);
   });
   // the reduce kernel (and so dw's summation order) is chosen from dw's own
   // size: with Cout % 4 == 0 the extra row never changes dw's bits (else the

@@ -160,7 +160,12 @@ void transpose_w_dgrad_launch(DT dt, const void* w, void* w_t2d, int KHW,
 void conv2d_dgrad_launch(DT dt, const void* dy, const void* w_t,
                          const void* w_t2d, void* dx, const void* zero16,
                          const ConvShape& cs, hipStream_t s);
-int conv2d_wgrad_zsplits(const ConvShape& cs);
+// kernel and split-M count of the wgrad launch for these arguments; the slab
+// workspace holds conv2d_wgrad_zsplits slabs (the one source of z)
+const char* conv2d_wgrad_route(DT dt, const void* x, const void* dy,
+                               const ConvShape& cs);
+int conv2d_wgrad_zsplits(DT dt, const void* x, const void* dy,
+                         const ConvShape& cs);
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
                          const ConvShape& cs, bool bias, hipStream_t s);

@@ -21,7 +21,9 @@
 //     defaults to the geometry above; the bf16 DMA-staged conv kernels also
 //     come in TileWide, 128x128 with 64x64 wave tiles (4x4 fragments), which
 //     stages two thirds of the bytes per FLOP. Both shapes share BK, the
-//     swizzled [rows][BK] image and the per-element MFMA sequence.
+//     swizzled [rows][BK] image and the per-element MFMA sequence. The
+//     k-major pieces of the bf16 wgrad (glds_stage_kmajor, tr_frags_wait)
+//     take the same tag.
 #pragma once
 
 #include "common.h"
@@ -398,8 +400,8 @@ DEV int kmaj_off(int row, int ch) {
 // source or the zero page; no exec masking). i = the wave's instruction
 // index, so callers can hoist per-instruction state out of the k-loop: a
 // lane's (row-in-tile, ch) never changes from chunk to chunk.
-template <int NCH, typename AddrFn>
-DEV void glds_stage_kmajor(bf16* img, const WaveCoord& w, AddrFn&& addr) {
+template <int NCH, typename S = TileStd, typename AddrFn>
+DEV void glds_stage_kmajor(bf16* img, const WaveCoordT<S>& w, AddrFn&& addr) {
   constexpr int RPK = 64 / NCH;                 // k-rows per 1 KiB region
   constexpr int NPW = BK * NCH * 16 / 1024 / 4;  // regions per wave
 #pragma unroll
@@ -455,13 +457,23 @@ DEV TrFrag tr_frag_issue(const bf16* img, int krow0, int col0, int lane) {
 
 // lgkmcnt(0) for the fragments of one k-step; the "+v" operands tie every
 // fragment to the wait, so no MFMA that consumes one is scheduled above it
-DEV void tr_frags_wait(TrFrag (&a)[FM], TrFrag (&b)[FN]) {
-  static_assert(FM == 4 && FN == 2, "operand list below");
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(a[0].lo), "+v"(a[0].hi), "+v"(a[1].lo), "+v"(a[1].hi),
-                 "+v"(a[2].lo), "+v"(a[2].hi), "+v"(a[3].lo), "+v"(a[3].hi),
-                 "+v"(b[0].lo), "+v"(b[0].hi), "+v"(b[1].lo), "+v"(b[1].hi)
-               :: "memory");
+template <typename S = TileStd>
+DEV void tr_frags_wait(TrFrag (&a)[S::FM], TrFrag (&b)[S::FN]) {
+  static_assert(S::FM == 4 && (S::FN == 2 || S::FN == 4),
+                "operand lists below");
+  if constexpr (S::FN == 2)
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a[0].lo), "+v"(a[0].hi), "+v"(a[1].lo), "+v"(a[1].hi),
+                   "+v"(a[2].lo), "+v"(a[2].hi), "+v"(a[3].lo), "+v"(a[3].hi),
+                   "+v"(b[0].lo), "+v"(b[0].hi), "+v"(b[1].lo), "+v"(b[1].hi)
+                 :: "memory");
+  else   // 16 tied operands, under the 30 an asm statement may have
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(a[0].lo), "+v"(a[0].hi), "+v"(a[1].lo), "+v"(a[1].hi),
+                   "+v"(a[2].lo), "+v"(a[2].hi), "+v"(a[3].lo), "+v"(a[3].hi),
+                   "+v"(b[0].lo), "+v"(b[0].hi), "+v"(b[1].lo), "+v"(b[1].hi),
+                   "+v"(b[2].lo), "+v"(b[2].hi), "+v"(b[3].lo), "+v"(b[3].hi)
+                 :: "memory");
 }
 
 // ---- column sums of a transposed B tile Bs[BN][BK] ------------------------
