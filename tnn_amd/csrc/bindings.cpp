@@ -415,10 +415,25 @@ at::Tensor mfma_selftest_f32(const at::Tensor& a, const at::Tensor& b) {
 }
 
 // ---- conv2d ----------------------------------------------------------------
+// The kernels take one ConvShape and trust it, so every entry point and its
+// *_route twin builds it here, and everything below raises before any launch.
 // shape of the conv whose input is [N, H, W, Cin] and output [N, OH, OW, Cout]
-static ConvShape conv_shape_out(int N, int H, int W, int Cin, int Cout, int KH,
-                                int KW, int SH, int SW, int PH, int PW, int OH,
-                                int OW) {
+static ConvShape conv_shape_out(const char* fn, int64_t N, int64_t H,
+                                int64_t W, int64_t Cin, int64_t Cout,
+                                int64_t KH, int64_t KW, int64_t SH, int64_t SW,
+                                int64_t PH, int64_t PW, int64_t OH,
+                                int64_t OW) {
+  TORCH_CHECK(SH >= 1 && SW >= 1, fn, ": stride must be >= 1, got (", SH,
+              ", ", SW, ")");
+  TORCH_CHECK(PH >= 0 && PW >= 0, fn, ": padding must be >= 0, got (", PH,
+              ", ", PW, ")");
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 &&
+                  KH >= 1 && KW >= 1,
+              fn, ": empty operand (N = ", N, ", H = ", H, ", W = ", W,
+              ", Cin = ", Cin, ", Cout = ", Cout, ", KH = ", KH, ", KW = ", KW,
+              ")");
+  TORCH_CHECK(OH >= 1 && OW >= 1, fn, ": no output pixel (OH = ", OH,
+              ", OW = ", OW, ")");
   ConvShape cs;
   cs.N = N;
   cs.H = H;
@@ -437,11 +452,77 @@ static ConvShape conv_shape_out(int N, int H, int W, int Cin, int Cout, int KH,
   return cs;
 }
 
-static ConvShape conv_shape(const at::Tensor& x, int Cin, int Cout, int KH,
-                            int KW, int SH, int SW, int PH, int PW) {
-  int H = x.size(1), W = x.size(2);
-  return conv_shape_out(x.size(0), H, W, Cin, Cout, KH, KW, SH, SW, PH, PW,
-                        (H + 2 * PH - KH) / SH + 1, (W + 2 * PW - KW) / SW + 1);
+// output extent of one axis; 0 where the padded input is shorter than the
+// kernel (C++ division would round -1 / 2 up to 0) or the stride is invalid
+static int64_t conv_out_extent(int64_t in, int64_t k, int64_t s, int64_t p) {
+  return s >= 1 && in + 2 * p >= k ? (in + 2 * p - k) / s + 1 : 0;
+}
+
+static ConvShape conv_shape(const char* fn, const at::Tensor& x, int64_t Cin,
+                            int64_t Cout, int64_t KH, int64_t KW, int64_t SH,
+                            int64_t SW, int64_t PH, int64_t PW) {
+  int64_t H = x.size(1), W = x.size(2);
+  return conv_shape_out(fn, x.size(0), H, W, Cin, Cout, KH, KW, SH, SW, PH, PW,
+                        conv_out_extent(H, KH, SH, PH),
+                        conv_out_extent(W, KW, SW, PW));
+}
+
+// operand checks and shape of conv2d_fwd / conv2d_fwd_stats / conv2d_fwd_route
+static ConvShape conv_fwd_shape(const char* fn, const at::Tensor& x,
+                                const at::Tensor& w, int64_t sh, int64_t sw,
+                                int64_t ph, int64_t pw) {
+  CHECK_IN(x);
+  CHECK_IN(w);
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && x.size(3) == w.size(2), fn,
+              " x ", x.sizes(), " w ", w.sizes());
+  TORCH_CHECK(x.scalar_type() == w.scalar_type(), fn, " dtype mismatch ",
+              x.scalar_type(), " vs ", w.scalar_type());
+  return conv_shape(fn, x, w.size(2), w.size(3), w.size(0), w.size(1), sh, sw,
+                    ph, pw);
+}
+
+// ... of conv2d_dgrad / conv2d_dgrad_route: dy's extents are those the conv
+// gives for (H, W), not whatever dy happens to have
+static ConvShape conv_dgrad_shape(const char* fn, const at::Tensor& dy,
+                                  const at::Tensor& w, int64_t H, int64_t W,
+                                  int64_t sh, int64_t sw, int64_t ph,
+                                  int64_t pw) {
+  CHECK_IN(dy);
+  CHECK_IN(w);
+  TORCH_CHECK(dy.dim() == 4 && w.dim() == 4, fn, " dy ", dy.sizes(), " w ",
+              w.sizes());
+  TORCH_CHECK(dy.scalar_type() == w.scalar_type(), fn,
+              " dtype mismatch: dy is ", dy.scalar_type(), ", w is ",
+              w.scalar_type());
+  TORCH_CHECK(dy.size(3) == w.size(3), fn, " dy ", dy.sizes(),
+              " has other channels than w ", w.sizes());
+  const int64_t KH = w.size(0), KW = w.size(1);
+  auto cs = conv_shape_out(fn, dy.size(0), H, W, w.size(2), w.size(3), KH, KW,
+                           sh, sw, ph, pw, conv_out_extent(H, KH, sh, ph),
+                           conv_out_extent(W, KW, sw, pw));
+  TORCH_CHECK(dy.size(1) == cs.OH && dy.size(2) == cs.OW, fn, " dy ",
+              dy.sizes(), " is not the output of a ", H, " x ", W,
+              " input: expected OH = ", cs.OH, ", OW = ", cs.OW);
+  return cs;
+}
+
+// ... of conv2d_wgrad / conv2d_wgrad_bias / conv2d_wgrad_route
+static ConvShape conv_wgrad_shape(const char* fn, const at::Tensor& x,
+                                  const at::Tensor& dy, int64_t KH, int64_t KW,
+                                  int64_t sh, int64_t sw, int64_t ph,
+                                  int64_t pw) {
+  CHECK_IN(x);
+  CHECK_IN(dy);
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4, fn, " x ", x.sizes(), " dy ",
+              dy.sizes());
+  TORCH_CHECK(x.scalar_type() == dy.scalar_type(), fn,
+              " dtype mismatch: x is ", x.scalar_type(), ", dy is ",
+              dy.scalar_type());
+  TORCH_CHECK(x.size(0) == dy.size(0), fn, " batch mismatch: x ", x.sizes(),
+              " dy ", dy.sizes());
+  auto cs = conv_shape(fn, x, x.size(3), dy.size(3), KH, KW, sh, sw, ph, pw);
+  TORCH_CHECK(dy.size(1) == cs.OH && dy.size(2) == cs.OW, "wgrad shape");
+  return cs;
 }
 
 // Returns {y, stats}. want_stats asks for the fused per-channel sum/sumsq
@@ -453,16 +534,15 @@ static std::vector<at::Tensor> conv2d_fwd_impl(
     const at::Tensor& x, const at::Tensor& w,
     const c10::optional<at::Tensor>& bias, int64_t sh, int64_t sw, int64_t ph,
     int64_t pw, bool relu, bool want_stats) {
-  CHECK_IN(x);
-  CHECK_IN(w);
-  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && x.size(3) == w.size(2),
-              "conv2d_fwd x ", x.sizes(), " w ", w.sizes());
-  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "conv2d dtype mismatch ",
-              x.scalar_type(), " vs ", w.scalar_type());
-  TORCH_CHECK(!bias.has_value() || bias->scalar_type() == x.scalar_type(),
-              "conv2d bias dtype mismatch");
-  auto cs = conv_shape(x, w.size(2), w.size(3), w.size(0), w.size(1), sh, sw,
-                       ph, pw);
+  auto cs = conv_fwd_shape("conv2d_fwd", x, w, sh, sw, ph, pw);
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->scalar_type() == x.scalar_type(),
+                "conv2d bias dtype mismatch");
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                    bias->numel() == cs.Cout,
+                "conv2d_fwd: bias must be a contiguous GPU tensor of ",
+                cs.Cout, " elements, got ", bias->sizes());
+  }
   auto y = at::empty({cs.N, cs.OH, cs.OW, cs.Cout}, x.options());
   at::Tensor wt2, stats;
   const bool db = conv2d_fwd_wants_db(dt_of(x), x.data_ptr(), cs);
@@ -505,11 +585,8 @@ std::vector<at::Tensor> conv2d_fwd_stats(const at::Tensor& x,
 at::Tensor conv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H,
                         int64_t W, int64_t sh, int64_t sw, int64_t ph,
                         int64_t pw) {
-  CHECK_IN(dy);
-  CHECK_IN(w);
-  int KH = w.size(0), KW = w.size(1), Cin = w.size(2), Cout = w.size(3);
-  auto cs = conv_shape_out(dy.size(0), H, W, Cin, Cout, KH, KW, sh, sw, ph, pw,
-                           dy.size(1), dy.size(2));
+  auto cs = conv_dgrad_shape("conv2d_dgrad", dy, w, H, W, sh, sw, ph, pw);
+  int KH = cs.KH, KW = cs.KW, Cin = cs.Cin, Cout = cs.Cout;
   auto dx = at::empty({cs.N, H, W, Cin}, dy.options());
   if (conv2d_dgrad_wants_db(dt_of(dy), dy.data_ptr(), cs)) {
     // double-buffered path: weight as [Cin][(kh,kw,co)] k-contiguous rows
@@ -534,10 +611,7 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H,
 std::string conv2d_fwd_route_name(const at::Tensor& x, const at::Tensor& w,
                                   int64_t sh, int64_t sw, int64_t ph,
                                   int64_t pw, bool stats) {
-  CHECK_IN(x);
-  CHECK_IN(w);
-  auto cs = conv_shape(x, w.size(2), w.size(3), w.size(0), w.size(1), sh, sw,
-                       ph, pw);
+  auto cs = conv_fwd_shape("conv2d_fwd_route", x, w, sh, sw, ph, pw);
   return conv2d_fwd_route(dt_of(x), x.data_ptr(), cs, stats);
 }
 
@@ -545,10 +619,8 @@ std::string conv2d_dgrad_route_name(const at::Tensor& dy,
                                     const at::Tensor& w, int64_t H, int64_t W,
                                     int64_t sh, int64_t sw, int64_t ph,
                                     int64_t pw) {
-  CHECK_IN(dy);
-  CHECK_IN(w);
-  auto cs = conv_shape_out(dy.size(0), H, W, w.size(2), w.size(3), w.size(0),
-                           w.size(1), sh, sw, ph, pw, dy.size(1), dy.size(2));
+  auto cs = conv_dgrad_shape("conv2d_dgrad_route", dy, w, H, W, sh, sw, ph,
+                             pw);
   return conv2d_dgrad_route(dt_of(dy), dy.data_ptr(), cs);
 }
 
@@ -557,9 +629,8 @@ std::string conv2d_dgrad_route_name(const at::Tensor& dy,
 std::tuple<std::string, int64_t> conv2d_wgrad_route_name(
     const at::Tensor& x, const at::Tensor& dy, int64_t KH, int64_t KW,
     int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
-  CHECK_IN(x);
-  CHECK_IN(dy);
-  auto cs = conv_shape(x, x.size(3), dy.size(3), KH, KW, sh, sw, ph, pw);
+  auto cs = conv_wgrad_shape("conv2d_wgrad_route", x, dy, KH, KW, sh, sw, ph,
+                             pw);
   return {conv2d_wgrad_route(dt_of(x), x.data_ptr(), dy.data_ptr(), cs),
           conv2d_wgrad_zsplits(dt_of(x), x.data_ptr(), dy.data_ptr(), cs)};
 }
@@ -569,10 +640,7 @@ static at::Tensor conv2d_wgrad_rows(const at::Tensor& x, const at::Tensor& dy,
                                     int64_t KH, int64_t KW, int64_t sh,
                                     int64_t sw, int64_t ph, int64_t pw,
                                     bool out_in_dt, bool bias) {
-  CHECK_IN(x);
-  CHECK_IN(dy);
-  auto cs = conv_shape(x, x.size(3), dy.size(3), KH, KW, sh, sw, ph, pw);
-  TORCH_CHECK(dy.size(1) == cs.OH && dy.size(2) == cs.OW, "wgrad shape");
+  auto cs = conv_wgrad_shape("conv2d_wgrad", x, dy, KH, KW, sh, sw, ph, pw);
   DT out_dt = out_in_dt ? dt_of(x) : DT::F32;
   const int64_t rows = KH * KW * cs.Cin + (bias ? 1 : 0);
   auto out = at::empty({rows, (int64_t)cs.Cout},

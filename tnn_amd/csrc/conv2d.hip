@@ -143,7 +143,9 @@ struct DgradClass {
   DEV DgradTap tap(const ConvShape& cs, int kidx) const {
     DgradTap t;
     if constexpr (S2) {
-      t.kwi = kidx & (nkw - 1);              // nkw is 1 or 2
+      // nkw is 1 or 2: dgrad_parity admits KW <= 4 only (nkw = 3 or 4 would
+      // need a real division here); nkh is free, khi takes what is left
+      t.kwi = kidx & (nkw - 1);
       t.khi = nkw == 2 ? (kidx >> 1) : kidx;
       t.kh = start_h + 2 * t.khi;
       t.kw = start_w + 2 * t.kwi;
@@ -1493,10 +1495,12 @@ bool conv2d_dgrad_wants_db(DT dt, const void* dy, const ConvShape& cs) {
          vec_ok(dt, dy, cs.Cout);
 }
 
-// the parity route's per-class shape; false where the route does not apply
+// the parity route's per-class shape; false where the route does not apply.
+// KW <= 4: a class then has at most 2 taps across, which is all that
+// DgradClass::tap decodes; wider kernels take the any-stride forms.
 static bool dgrad_parity(const ConvShape& cs, ConvShape& cs2) {
   bool s2 = all_pow2(cs) && cs.SH == 2 && cs.SW == 2 && cs.H % 2 == 0 &&
-            cs.W % 2 == 0;
+            cs.W % 2 == 0 && cs.KW <= 4;
   cs2 = cs;
   if (s2) {
     cs2.d_hw.set((cs.H / 2) * (cs.W / 2));
@@ -1508,9 +1512,9 @@ static bool dgrad_parity(const ConvShape& cs, ConvShape& cs2) {
 
 // Route, first match (w_t2d is passed iff conv2d_dgrad_wants_db: switch on,
 // all-pow2, vector gate, KH*KW*Cout <= TNN_DB_MAXK_DGRAD; else w_t).
-// parity = all-pow2, stride 2x2, even H and W, pow2 per-class divisors: 4
-// classes in grid.z over an M/4-row problem (see DgradClass), cs with the
-// per-class divisors.
+// parity = all-pow2, stride 2x2, even H and W, KW <= 4, pow2 per-class
+// divisors: 4 classes in grid.z over an M/4-row problem (see DgradClass), cs
+// with the per-class divisors.
 // wide: bf16, Cin % 128 == 0 and TNN_CONV_WIDE says so (dgrad_wide); the wide
 // routes take the same parity / stride-1 / any-stride forms:
 //   w_t2d, wide, K <= 1152        k_conv_dgrad_sb_wide<S2, S1>
