@@ -198,6 +198,24 @@ __global__ void k_bn_bwd_reduce_vec(const T* __restrict__ x,
 
 // shift: row 0 of x when sum/sumsq are moments of x - shift[c]; null for
 // raw moments (the conv-epilogue sums)
+// channel c from its sum and sumsq (of x - shift): mean, invstd and the fused
+// running-stat update (unbiased var, torch semantics)
+DEV void bn_finalize_channel(int c, float sum, float sumsq, float shift,
+                             float* mean, float* invstd, float* rmean,
+                             float* rvar, float momentum, int64_t rows,
+                             float eps) {
+  float d = sum / rows;  // mean - shift
+  float var = fmaxf(sumsq / rows - d * d, 0.0f);
+  float m = shift + d;
+  mean[c] = m;
+  invstd[c] = rsqrtf(var + eps);
+  if (rmean) {
+    float unbiased = var * ((float)rows / (float)(rows > 1 ? rows - 1 : 1));
+    rmean[c] = rmean[c] * (1.0f - momentum) + m * momentum;
+    rvar[c] = rvar[c] * (1.0f - momentum) + unbiased * momentum;
+  }
+}
+
 template <typename T>
 __global__ void k_bn_finalize(float* mean, float* invstd, const float* sum,
                               const float* sumsq, const T* shift, float* rmean,
@@ -205,16 +223,49 @@ __global__ void k_bn_finalize(float* mean, float* invstd, const float* sum,
                               int cols, float eps) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
-  float d = sum[c] / rows;  // mean - shift
-  float var = fmaxf(sumsq[c] / rows - d * d, 0.0f);
-  float m = shift ? VecIO<T>::to_f32(shift[c]) + d : d;
-  mean[c] = m;
-  invstd[c] = rsqrtf(var + eps);
-  if (rmean) {  // fused running-stat update (unbiased var, torch semantics)
-    float unbiased = var * ((float)rows / (float)(rows > 1 ? rows - 1 : 1));
-    rmean[c] = rmean[c] * (1.0f - momentum) + m * momentum;
-    rvar[c] = rvar[c] * (1.0f - momentum) + unbiased * momentum;
+  if (shift)
+    bn_finalize_channel(c, sum[c], sumsq[c], VecIO<T>::to_f32(shift[c]), mean,
+                        invstd, rmean, rvar, momentum, rows, eps);
+  else
+    bn_finalize_channel(c, sum[c], sumsq[c], 0.0f, mean, invstd, rmean, rvar,
+                        momentum, rows, eps);
+}
+
+// fold + finalize of [S][2][C] raw-moment partials (the conv epilogue's) in
+// one launch. The fold has k_slab_fin's shape and, for the CPB that
+// slab_fin_launch picks for 2C columns, its summation order per column: 256 /
+// CPB thread-rows take every RPB-th slice, then an LDS tree. So mean, invstd
+// and the running statistics are bitwise those of slab_fin_launch followed
+// by k_bn_finalize. A block owns CPB channels and folds their sum and sumsq
+// columns one after the other.
+template <int CPB>
+__global__ void k_bn_finalize_fold(const float* __restrict__ part, int S,
+                                   float* mean, float* invstd, float* rmean,
+                                   float* rvar, float momentum, int64_t rows,
+                                   int C, float eps) {
+  constexpr int RPB = 256 / CPB;
+  __shared__ float sh[2][256];
+  const int cl = threadIdx.x % CPB;
+  const int sl = threadIdx.x / CPB;
+  const int c = blockIdx.x * CPB + cl;
+  float a = 0.0f, b = 0.0f;
+  if (c < C) {
+    for (int s = sl; s < S; s += RPB) a += part[(int64_t)s * 2 * C + c];
+    for (int s = sl; s < S; s += RPB) b += part[(int64_t)s * 2 * C + C + c];
   }
+  sh[0][sl * CPB + cl] = a;
+  sh[1][sl * CPB + cl] = b;
+  __syncthreads();
+  for (int h = RPB / 2; h > 0; h >>= 1) {
+    if (sl < h) {
+      sh[0][sl * CPB + cl] += sh[0][(sl + h) * CPB + cl];
+      sh[1][sl * CPB + cl] += sh[1][(sl + h) * CPB + cl];
+    }
+    __syncthreads();
+  }
+  if (sl == 0 && c < C)
+    bn_finalize_channel(c, sh[0][cl], sh[1][cl], 0.0f, mean, invstd, rmean,
+                        rvar, momentum, rows, eps);
 }
 
 template <typename T>
@@ -556,6 +607,25 @@ void bn_finalize_launch(const float* sum, const float* sumsq, float* mean,
                      eps);
 }
 
+void bn_finalize_fold_launch(const float* partials, int slices, float* mean,
+                             float* invstd, float* rmean, float* rvar,
+                             float momentum, int64_t rows, int cols, float eps,
+                             hipStream_t s) {
+  // CPB as slab_fin_launch picks it for the 2 * cols columns of the partials
+  const int c2 = 2 * cols;
+#define FOLD_CASE(CPB)                                                       \
+  hipLaunchKernelGGL(k_bn_finalize_fold<CPB>, dim3((cols + CPB - 1) / CPB), \
+                     dim3(256), 0, s, partials, slices, mean, invstd, rmean, \
+                     rvar, momentum, rows, cols, eps)
+  if (c2 >= 128 * 32) FOLD_CASE(32);
+  else if (c2 >= 128 * 16) FOLD_CASE(16);
+  else if (c2 >= 128 * 8) FOLD_CASE(8);
+  else if (c2 >= 128 * 4) FOLD_CASE(4);
+  else if (c2 >= 128 * 2) FOLD_CASE(2);
+  else FOLD_CASE(1);
+#undef FOLD_CASE
+}
+
 void bn_apply_launch(DT dt, const void* x, const float* mean,
                      const float* invstd, const float* gamma, const float* beta,
                      void* y, int64_t rows, int cols, bool relu,
@@ -649,7 +719,9 @@ void bn_bwd_reduce_launch(DT dt, const void* x, const void* dy,
                           const void* y_relu, const float* mean,
                           const float* invstd, float* sum_dy,
                           float* sum_dy_xhat, float* ws, int64_t rows,
-                          int cols, float dy_scale, hipStream_t s) {
+                          int cols, float dy_scale, hipStream_t s,
+                          float* dgamma_out, float* dbeta_out,
+                          bool accumulate) {
   if (ws) {
     // vec path: slabs (plain stores) + slab finalize into the contiguous
     // {2, C} sums buffer (sum_dy_xhat == sum_dy + C)
@@ -664,7 +736,9 @@ void bn_bwd_reduce_launch(DT dt, const void* x, const void* dy,
       hipLaunchKernelGGL(k_bn_bwd_reduce_vec<bf16>, g, dim3(256), 0, s,
                          (const bf16*)x, (const bf16*)dy, (const bf16*)y_relu,
                          mean, invstd, ws, nullptr, rows, cols, dy_scale);
-    slab_fin_launch(ws, sum_dy, (int)g.y, 2 * cols, s);
+    // first half of the columns is sum_dy (dbeta), second sum_dy_xhat (dgamma)
+    slab_fin_launch(ws, sum_dy, (int)g.y, 2 * cols, s, dbeta_out, dgamma_out,
+                    accumulate);
     return;
   }
   if (dt == DT::F32)

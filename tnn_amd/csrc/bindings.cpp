@@ -525,8 +525,10 @@ static ConvShape conv_wgrad_shape(const char* fn, const at::Tensor& x,
   return cs;
 }
 
-// Returns {y, stats}. want_stats asks for the fused per-channel sum/sumsq
-// [2, Cout] of y (linear act); it comes from the DMA-staged kernels only
+// Returns {y, stats}. want_stats asks for the fused per-channel sum/sumsq of
+// y (linear act) as slab partials [m-tiles, 2, Cout], one row per 128-row
+// m-tile, written with plain stores into an at::empty tensor (no atomics, no
+// zero-init; a fold sums the rows). It comes from the DMA-staged kernels only
 // (k_conv_fwd_db / k_conv_fwd_sb), so where those are not eligible (non-pow2
 // dims, unaligned x, fp32 with K > 2304, TNN_FWD_DB=0) stats is EMPTY and y
 // is computed by the plain route all the same.
@@ -553,7 +555,8 @@ static std::vector<at::Tensor> conv2d_fwd_impl(
                            cs.KH * cs.KW, cs.Cin, cs.Cout, cur_stream());
   }
   if (want_stats)
-    stats = db ? at::zeros({2, (int64_t)cs.Cout},
+    stats = db ? at::empty({(int64_t)conv2d_fwd_stats_rows(cs), 2,
+                            (int64_t)cs.Cout},
                            x.options().dtype(at::kFloat))
                : at::empty({0}, x.options().dtype(at::kFloat));
   conv2d_fwd_launch(dt_of(x), x.data_ptr(), w.data_ptr(),
@@ -579,6 +582,24 @@ std::vector<at::Tensor> conv2d_fwd_stats(const at::Tensor& x,
                                          const c10::optional<at::Tensor>& bias,
                                          int64_t sh, int64_t sw, int64_t ph,
                                          int64_t pw) {
+  auto out = conv2d_fwd_impl(x, w, bias, sh, sw, ph, pw, /*relu=*/false, true);
+  if (out[1].numel()) {
+    // partials -> [2, Cout], the fold bn_fwd_train does on the partials
+    auto stats = at::empty({2, out[1].size(2)}, out[1].options());
+    slab_fin_launch(out[1].data_ptr<float>(), stats.data_ptr<float>(),
+                    (int)out[1].size(0), (int)(2 * out[1].size(2)),
+                    cur_stream());
+    out[1] = stats;
+  }
+  return out;
+}
+
+// the same with the statistics left as partials [m-tiles, 2, Cout] (empty when
+// ineligible), for bn_fwd_train(precomp=...), which folds them in its finalize
+std::vector<at::Tensor> conv2d_fwd_partials(
+    const at::Tensor& x, const at::Tensor& w,
+    const c10::optional<at::Tensor>& bias, int64_t sh, int64_t sw, int64_t ph,
+    int64_t pw) {
   return conv2d_fwd_impl(x, w, bias, sh, sw, ph, pw, /*relu=*/false, true);
 }
 
@@ -680,6 +701,80 @@ std::vector<at::Tensor> conv2d_wgrad_bias(const at::Tensor& x,
           out.select(0, kout)};
 }
 
+// A gradient destination handed to an into-variant: a contiguous GPU tensor
+// of the given dtype and shape, on the operand's device.
+static void check_grad_dst(const char* fn, const char* name,
+                           const at::Tensor& t, const at::Tensor& like,
+                           at::ScalarType st, at::IntArrayRef shape) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), fn, ": ", name,
+              " must be a GPU tensor on ", like.device());
+  TORCH_CHECK(t.scalar_type() == st, fn, ": ", name, " must be ", st, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.sizes() == shape, fn, ": ", name, " must have shape ", shape,
+              ", got ", t.sizes());
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+}
+
+// splitk_reduce_can_split on plain integers (host arithmetic only; the
+// addresses are byte addresses): whether a reduce of n elements can put
+// [0, n0) at addr0 and [n0, n) at addr1 for fp32 (or bf16) output
+bool splitk_can_split(int64_t n, int64_t n0, int64_t addr0, int64_t addr1,
+                      bool bf16_out) {
+  return splitk_reduce_can_split(n, n0, (const void*)(uintptr_t)addr0,
+                                 (const void*)(uintptr_t)addr1,
+                                 bf16_out ? DT::BF16 : DT::F32);
+}
+
+// conv2d_wgrad / conv2d_wgrad_bias with the split reduce writing straight
+// into the parameters' gradient buffers: dw_out [KH, KW, Cin, Cout] and
+// db_out [Cout] (optional), both of one dtype (x's, or fp32). accumulate adds
+// the fp32 sum to what they hold and rounds once. Route, z and workspace are
+// those of conv2d_wgrad_bias, so the bits are too.
+void conv2d_wgrad_into(const at::Tensor& x, const at::Tensor& dy, int64_t KH,
+                       int64_t KW, int64_t sh, int64_t sw, int64_t ph,
+                       int64_t pw, at::Tensor dw_out,
+                       const c10::optional<at::Tensor>& db_out,
+                       bool accumulate) {
+  const char* fn = "conv2d_wgrad_into";
+  auto cs = conv_wgrad_shape(fn, x, dy, KH, KW, sh, sw, ph, pw);
+  const auto st = dw_out.scalar_type();
+  TORCH_CHECK(st == x.scalar_type() || st == at::kFloat, fn,
+              ": dw_out must be ", x.scalar_type(), " or Float, got ", st);
+  check_grad_dst(fn, "dw_out", dw_out, x, st,
+                 {KH, KW, (int64_t)cs.Cin, (int64_t)cs.Cout});
+  const bool bias = db_out.has_value();
+  if (bias) check_grad_dst(fn, "db_out", *db_out, x, st, {(int64_t)cs.Cout});
+  const DT out_dt = st == at::kFloat ? DT::F32 : dt_of(x);
+  const int64_t kout = KH * KW * cs.Cin;
+  const int64_t rows = kout + (bias ? 1 : 0);
+  const int z = conv2d_wgrad_zsplits(dt_of(x), x.data_ptr(), dy.data_ptr(), cs);
+  auto ws = at::empty({(int64_t)z * rows * cs.Cout},
+                      x.options().dtype(at::kFloat));
+  void* dbp = bias ? db_out->data_ptr() : nullptr;
+  if (splitk_reduce_can_split(rows * cs.Cout, kout * cs.Cout,
+                              dw_out.data_ptr(), bias ? dbp : dw_out.data_ptr(),
+                              out_dt)) {
+    WgradSink sink{dbp, accumulate};
+    conv2d_wgrad_launch(dt_of(x), x.data_ptr(), dy.data_ptr(),
+                        dw_out.data_ptr(), out_dt, ws.data_ptr<float>(), z,
+                        zero_page(x), cs, bias, cur_stream(), &sink);
+    return;
+  }
+  // the float4 reduce cannot split here (dw/db boundary or a destination off
+  // a group of 4): reduce the old way into one fp32 tensor, then copy or add
+  auto tmp = at::empty({rows, (int64_t)cs.Cout}, ws.options());
+  WgradSink one{nullptr, false};
+  conv2d_wgrad_launch(dt_of(x), x.data_ptr(), dy.data_ptr(), tmp.data_ptr(),
+                      DT::F32, ws.data_ptr<float>(), z, zero_page(x), cs, bias,
+                      cur_stream(), &one);
+  auto put = [&](at::Tensor dst, const at::Tensor& src) {
+    dst.copy_(accumulate ? dst.to(at::kFloat).add_(src.view(dst.sizes()))
+                         : src.view(dst.sizes()));
+  };
+  put(dw_out, tmp.narrow(0, 0, kout));
+  if (bias) put(*db_out, tmp.select(0, kout));
+}
+
 // ---- batch norm ------------------------------------------------------------
 std::vector<at::Tensor> bn_fwd_train(const at::Tensor& x,
                                      const at::Tensor& gamma,
@@ -701,12 +796,27 @@ std::vector<at::Tensor> bn_fwd_train(const at::Tensor& x,
   float* rm = rmean.has_value() ? rmean->data_ptr<float>() : nullptr;
   float* rv = rvar.has_value() ? rvar->data_ptr<float>() : nullptr;
   if (precomp.has_value()) {
-    // sums already produced by the conv epilogue ({2, C}: sum, sumsq)
-    TORCH_CHECK(precomp->numel() == 2 * C, "bad precomputed stats");
+    // sums already produced by the conv epilogue: {2, C} (sum, sumsq), or
+    // its slab partials {R, 2, C}, folded inside the finalize kernel
+    TORCH_CHECK(precomp->is_cuda() && precomp->is_contiguous() &&
+                    precomp->scalar_type() == at::kFloat,
+                "bn_fwd_train: precomp must be a contiguous fp32 GPU tensor");
+    const bool partials = precomp->dim() == 3;
+    TORCH_CHECK(partials ? precomp->size(0) >= 1 && precomp->size(1) == 2 &&
+                               precomp->size(2) == C
+                         : precomp->numel() == 2 * C,
+                "bad precomputed stats: ", precomp->sizes(), " for C = ", C);
     const float* ps = precomp->data_ptr<float>();
-    bn_finalize_launch(ps, ps + C, mean.data_ptr<float>(),
-                       invstd.data_ptr<float>(), rm, rv, (float)momentum,
-                       rows, C, (float)eps, cur_stream());
+    if (partials)
+      bn_finalize_fold_launch(ps, (int)precomp->size(0),
+                              mean.data_ptr<float>(),
+                              invstd.data_ptr<float>(), rm, rv,
+                              (float)momentum, rows, C, (float)eps,
+                              cur_stream());
+    else
+      bn_finalize_launch(ps, ps + C, mean.data_ptr<float>(),
+                         invstd.data_ptr<float>(), rm, rv, (float)momentum,
+                         rows, C, (float)eps, cur_stream());
   } else {
     const int64_t wsn = bn_stats_ws_floats(dt_of(x), x.data_ptr(), rows, C);
     at::Tensor ws;
@@ -754,7 +864,12 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
                                const c10::optional<at::Tensor>& y_relu,
                                double dy_scale,
                                const c10::optional<at::Tensor>& resid =
-                                   c10::nullopt) {
+                                   c10::nullopt,
+                               const c10::optional<at::Tensor>& dgamma_out =
+                                   c10::nullopt,
+                               const c10::optional<at::Tensor>& dbeta_out =
+                                   c10::nullopt,
+                               bool accumulate = false) {
   CHECK_IN(x);
   CHECK_IN(dy);
   const void* resp = nullptr;
@@ -774,6 +889,20 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
                   : at::zeros({2, C}, x.options().dtype(at::kFloat));
   auto sum_dy = sums[0];
   auto sum_dy_xhat = sums[1];
+  // gradient sinks: the slab finalize also writes (or adds) dgamma / dbeta
+  // into these fp32 [C] buffers. Slab path only (bn_bwd_takes_sink): the
+  // scalar-atomics fallback returns its sums and nothing else.
+  float *dgp = nullptr, *dbp = nullptr;
+  TORCH_CHECK(dgamma_out.has_value() == dbeta_out.has_value(),
+              "bn_bwd: dgamma_out and dbeta_out go together");
+  if (dgamma_out.has_value()) {
+    TORCH_CHECK(wsn, "bn_bwd: no gradient sink on the scalar path "
+                     "(ask bn_bwd_takes_sink first)");
+    check_grad_dst("bn_bwd", "dgamma_out", *dgamma_out, x, at::kFloat, {C});
+    check_grad_dst("bn_bwd", "dbeta_out", *dbeta_out, x, at::kFloat, {C});
+    dgp = dgamma_out->data_ptr<float>();
+    dbp = dbeta_out->data_ptr<float>();
+  }
   at::Tensor ws;
   float* wp = nullptr;
   if (wsn) {
@@ -785,7 +914,8 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
   bn_bwd_reduce_launch(dt_of(x), x.data_ptr(), dy.data_ptr(), yr,
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
                        sum_dy.data_ptr<float>(), sum_dy_xhat.data_ptr<float>(),
-                       wp, rows, C, (float)dy_scale, cur_stream());
+                       wp, rows, C, (float)dy_scale, cur_stream(), dgp, dbp,
+                       accumulate);
   bn_bwd_apply_launch(dt_of(x), x.data_ptr(), dy.data_ptr(), yr,
                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
                       gamma.data_ptr<float>(), sum_dy.data_ptr<float>(),
@@ -793,6 +923,16 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x, const at::Tensor& dy,
                       rows, C, (float)dy_scale, cur_stream());
   // dgamma = sum_dy_xhat, dbeta = sum_dy (fp32, matching fp32 gamma/beta)
   return {dx, sum_dy_xhat, sum_dy};
+}
+
+// whether bn_bwd of these operands runs the slab path, which alone can write
+// dgamma_out / dbeta_out
+bool bn_bwd_takes_sink(const at::Tensor& x, const at::Tensor& dy) {
+  CHECK_IN(x);
+  CHECK_IN(dy);
+  const int C = x.size(-1);
+  return bn_bwd_ws_floats(dt_of(x), x.data_ptr(), dy.data_ptr(),
+                          x.numel() / C, C) != 0;
 }
 
 // ---- pooling ---------------------------------------------------------------
@@ -1604,12 +1744,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_selftest_f32", &tnn::mfma_selftest_f32);
   m.def("conv2d_fwd", &tnn::conv2d_fwd);
   m.def("conv2d_fwd_stats", &tnn::conv2d_fwd_stats);
+  m.def("conv2d_fwd_partials", &tnn::conv2d_fwd_partials);
   m.def("conv2d_dgrad", &tnn::conv2d_dgrad);
   m.def("conv2d_fwd_route", &tnn::conv2d_fwd_route_name);
   m.def("conv2d_dgrad_route", &tnn::conv2d_dgrad_route_name);
   m.def("conv2d_wgrad_route", &tnn::conv2d_wgrad_route_name);
   m.def("conv2d_wgrad", &tnn::conv2d_wgrad);
   m.def("conv2d_wgrad_bias", &tnn::conv2d_wgrad_bias);
+  m.def("conv2d_wgrad_into", &tnn::conv2d_wgrad_into, py::arg("x"),
+        py::arg("dy"), py::arg("KH"), py::arg("KW"), py::arg("sh"),
+        py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("dw_out"),
+        py::arg("db_out") = py::none(), py::arg("accumulate") = false);
+  m.def("bn_bwd_takes_sink", &tnn::bn_bwd_takes_sink);
+  m.def("splitk_can_split", &tnn::splitk_can_split);
   m.def("bn_fwd_train", &tnn::bn_fwd_train, py::arg("x"), py::arg("gamma"),
         py::arg("beta"), py::arg("rmean"), py::arg("rvar"),
         py::arg("momentum"), py::arg("eps"), py::arg("relu"),
@@ -1619,7 +1766,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd", &tnn::bn_bwd, py::arg("x"), py::arg("dy"),
         py::arg("gamma"), py::arg("mean"), py::arg("invstd"),
         py::arg("y_relu"), py::arg("dy_scale"),
-        py::arg("resid") = py::none());
+        py::arg("resid") = py::none(), py::arg("dgamma_out") = py::none(),
+        py::arg("dbeta_out") = py::none(), py::arg("accumulate") = false);
   m.def("maxpool_fwd", &tnn::maxpool_fwd);
   m.def("maxpool_bwd", &tnn::maxpool_bwd);
   m.def("avgpool_fwd", &tnn::avgpool_fwd);

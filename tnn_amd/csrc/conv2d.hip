@@ -262,19 +262,27 @@ DEV void conv_fwd_store(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN],
 // fwd fused statistics: per-channel sum/sumsq of the tile straight from the
 // accumulators (post-bias, linear act only): saves the BN stats pass's full
 // read of y. C/D fragment col = lane&15; lanes {l, l+16, l+32, l+48} share
-// a column -> two shfl_xor folds, then one atomic per (block, col).
+// a column -> two shfl_xor folds give one partial per (wave, col). The
+// WAVES_M waves of the block that share a column fold through a small LDS
+// array of its own (2 KB; the k-loop's buffers are not touched), in wave
+// order, and the block stores one [2][BN] partial with plain stores into
+// partials[tm][2][Cout], tm the m-tile after the tile-order remap. No atomics,
+// no zero-init: every (tm, col) is written by exactly one block, and the rows
+// are summed by a fold in a fixed order (slab_fin_launch / k_bn_finalize_fold),
+// so two calls give the same bits. Every thread of the block must call this.
 template <typename T, typename S>
 DEV void conv_fwd_stats(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN],
-                        const T* bias_p, float* stats, const ConvShape& cs,
-                        int m0, int n0, int M) {
+                        const T* bias_p, float* partials, const ConvShape& cs,
+                        int tm, int m0, int n0, int M) {
   constexpr int FM = S::FM, FN = S::FN;
-  float* ssum = stats;
-  float* ssumsq = stats + cs.Cout;
+  __shared__ float red[2][S::WAVES_M][S::BN];
+  const int wm = wc.wid / S::WAVES_N;
   const int cr = (wc.lane >> 4) * 4;
   const int cc = wc.lane & 15;
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) {
-    int col = n0 + wc.wcol0 + fn * 16 + cc;
+    const int lcol = wc.wcol0 + fn * 16 + cc;
+    int col = n0 + lcol;
     float bias = 0.0f;
     if (col < cs.Cout) {
       if (bias_p) bias = VecIO<T>::to_f32(bias_p[col]);
@@ -295,10 +303,20 @@ DEV void conv_fwd_stats(const WaveCoordT<S>& wc, f32x4 acc[S::FM][S::FN],
     ss += __shfl_xor(ss, 16, 64);
     s += __shfl_xor(s, 32, 64);
     ss += __shfl_xor(ss, 32, 64);
-    if (wc.lane < 16 && col < cs.Cout) {
-      atomicAdd(&ssum[col], s);
-      atomicAdd(&ssumsq[col], ss);
+    if (wc.lane < 16) {
+      red[0][wm][lcol] = s;
+      red[1][wm][lcol] = ss;
     }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * S::BN; i += THREADS) {
+    const int which = i / S::BN, lcol = i % S::BN;
+    const int col = n0 + lcol;
+    if (col >= cs.Cout) continue;
+    float a = red[which][0][lcol];
+#pragma unroll
+    for (int w = 1; w < S::WAVES_M; ++w) a += red[which][w][lcol];
+    partials[((int64_t)tm * 2 + which) * cs.Cout + col] = a;
   }
 }
 
@@ -558,7 +576,8 @@ DEV void conv_fwd_glds_tile(const T* __restrict__ X,
   }
 
   conv_fwd_store(wc, acc, bias, Y, cs, act_kind, m0, n0, M);
-  if constexpr (STATS) conv_fwd_stats(wc, acc, bias, stats, cs, m0, n0, M);
+  if constexpr (STATS)
+    conv_fwd_stats(wc, acc, bias, stats, cs, tm_, m0, n0, M);
 }
 
 template <typename T, bool STATS = false>
@@ -1314,6 +1333,13 @@ static int wide_buf() {
   return buf;
 }
 
+// rows of the fused-statistics partials [rows][2][Cout]: one per m-tile (both
+// block tiles are 128 rows tall)
+int conv2d_fwd_stats_rows(const ConvShape& cs) {
+  static_assert(TileWide::BM == BM, "one m-tile height for the partials");
+  return ceil_div(cs.N * cs.OH * cs.OW, BM);
+}
+
 // The wide tile is eligible for a bf16 GEMM view [M, N, K] on the DMA-staged
 // route when N % 128 == 0 (no N tail). What auto does with an eligible shape
 // was fixed from the per-shape table in profiles/prof_wrn_conv_wide.md
@@ -1330,15 +1356,19 @@ static Wide wide_pick(bool eligible, int tiles, bool take, bool single) {
   return single ? Wide::SB : Wide::DB;
 }
 // forward, K = KH*KW*Cin:
-//   one n-tile (Cout == 128)   one buffer pair wins 8-9 %; not with fused
-//                              statistics, whose atomics then cost more than
-//                              the tile saves (g1: 148 -> 190 us)
+//   one n-tile (Cout == 128)   one buffer pair wins 8-9 %, and with fused
+//                              statistics 5-6 % (g1: 125.5-126.8 -> 118.8-
+//                              119.4 us, g1 entry 53.7-54.1 -> 50.8-52.0,
+//                              profiles/prof_wrn_grad_sink.md) now that the
+//                              statistics are slab partials; with atomics the
+//                              wide tile lost there (148 -> 190 us)
 //   more n-tiles               the double buffer wins 11-26 % from K = 2304
 //                              up; below that (K <= 1152) nothing wins
-static Wide fwd_wide(DT dt, bool have_wt2, const ConvShape& cs, bool stats) {
+// The choice does not depend on whether statistics are fused.
+static Wide fwd_wide(DT dt, bool have_wt2, const ConvShape& cs) {
   const int nt = cs.Cout / TileWide::BN;
   const int K = cs.KH * cs.KW * cs.Cin;
-  const bool take = nt == 1 ? !stats : K >= WIDE_FWD_DB_MINK;
+  const bool take = nt == 1 || K >= WIDE_FWD_DB_MINK;
   return wide_pick(
       have_wt2 && dt == DT::BF16 && cs.Cout % TileWide::BN == 0,
       ceil_div(cs.N * cs.OH * cs.OW, TileWide::BM) * nt, take, nt == 1);
@@ -1421,7 +1451,7 @@ enum class FwdRoute { SB_WIDE, DB_WIDE, SB, DB, GLDS, POW2, GENERIC };
 static FwdRoute fwd_route(DT dt, const void* x, bool have_wt2,
                           const ConvShape& cs, bool stats) {
   if (have_wt2) {
-    const Wide wide = fwd_wide(dt, true, cs, stats);
+    const Wide wide = fwd_wide(dt, true, cs);
     if (wide != Wide::NO)
       return wide == Wide::SB ? FwdRoute::SB_WIDE : FwdRoute::DB_WIDE;
     const bool long_k =
@@ -1735,16 +1765,23 @@ const char* conv2d_wgrad_route(DT dt, const void* x, const void* dy,
 }
 
 // z: conv2d_wgrad_zsplits of the same arguments (the workspace holds z slabs)
+// sink: dw_out is a parameter's gradient buffer ([Kout][Cout] only) and the
+// bias row, if asked for, goes to sink->db_out; sink->accumulate adds to what
+// both hold. Same route, z and workspace: only the reduce's destinations
+// differ. A sink always takes the workspace plus the reduce, also where
+// z == 1 with fp32 output would write dw_out directly: the direct tile is
+// [Kout+1][Cout] in one piece and cannot add to a gradient.
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
-                         const ConvShape& cs, bool bias, hipStream_t s) {
+                         const ConvShape& cs, bool bias, hipStream_t s,
+                         const WgradSink* sink) {
   int Kout = cs.KH * cs.KW * cs.Cin;
   // bias: dw_out and every slab carry one more row, [Kout+1][Cout], whose
   // last row is the bias gradient sum_m dy (summed by the tile-row-0 blocks)
   const int bias_row = bias ? 1 : 0;
   // bf16 output always goes through the (casting) reduce; fp32 with z==1
   // writes the slab target directly
-  bool direct = z == 1 && out_dt == DT::F32;
+  bool direct = z == 1 && out_dt == DT::F32 && !sink;
   float* target = direct ? (float*)dw_out : ws;
   dim3 grid(ceil_div(Kout, BM), ceil_div(cs.Cout, BN), z);
   const WgradRoute route = wgrad_route(dt, x, dy, cs);
@@ -1780,7 +1817,9 @@ void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
   if (!direct)
     splitk_reduce_launch(ws, dw_out, out_dt, z,
                          (int64_t)(Kout + bias_row) * cs.Cout, s,
-                         (int64_t)Kout * cs.Cout);
+                         (int64_t)Kout * cs.Cout,
+                         sink && bias ? sink->db_out : nullptr,
+                         (int64_t)Kout * cs.Cout, sink && sink->accumulate);
 }
 
 }  // namespace tnn

@@ -228,9 +228,14 @@ void dropout_bwd_launch(DT dt, const void* dy, const uint8_t* mask, void* dx,
 // replacing per-(block,col) atomics whose same-address serialization cost
 // a fixed ~20-50us at 512 row slices, and the at::zeros the atomics
 // needed). Block owns 32 columns; 8 thread-rows split the S range.
+// d0 / d1: a second home for the two halves of the columns (BN backward:
+// dbeta, dgamma in the parameters' gradient buffers), written or, with acc,
+// added to; nullptr for every other caller.
 template <int CPB>  // columns per block; 256/CPB threads fold slices per col
 __global__ void k_slab_fin(const float* __restrict__ ws,
-                           float* __restrict__ out, int S, int C2) {
+                           float* __restrict__ out, int S, int C2,
+                           float* __restrict__ d0, float* __restrict__ d1,
+                           int acc) {
   constexpr int RPB = 256 / CPB;
   __shared__ float sh[256];
   const int cl = threadIdx.x % CPB;
@@ -246,17 +251,25 @@ __global__ void k_slab_fin(const float* __restrict__ ws,
     if (sl < h) sh[sl * CPB + cl] += sh[(sl + h) * CPB + cl];
     __syncthreads();
   }
-  if (sl == 0 && c < C2) out[c] = sh[cl];
+  if (sl == 0 && c < C2) {
+    const float v = sh[cl];
+    out[c] = v;
+    if (d0) {
+      const int C = C2 >> 1;
+      float* d = c < C ? d0 + c : d1 + (c - C);
+      *d = acc ? *d + v : v;
+    }
+  }
 }
 
 void slab_fin_launch(const float* ws, float* out, int slices, int c2,
-                     hipStream_t s) {
+                     hipStream_t s, float* d0, float* d1, bool accumulate) {
   // pick columns-per-block so ~128+ blocks launch regardless of C: the
   // slice fold is latency-bound and needs the parallelism spread over
   // slices, not columns
 #define SLAB_CASE(CPB)                                                       \
   hipLaunchKernelGGL(k_slab_fin<CPB>, dim3((c2 + CPB - 1) / CPB), dim3(256), \
-                     0, s, ws, out, slices, c2)
+                     0, s, ws, out, slices, c2, d0, d1, accumulate ? 1 : 0)
   if (c2 >= 128 * 32) SLAB_CASE(32);
   else if (c2 >= 128 * 16) SLAB_CASE(16);
   else if (c2 >= 128 * 8) SLAB_CASE(8);

@@ -5,6 +5,7 @@
 // (src/math/cuda/gemm.cu:64, src/math/cuda/cudnn_gemm.cu:285,
 // src/nn/layers_impl/cuda/dense_ops.cu:17-117).
 
+#include <stdexcept>
 #include "common.h"
 #include "kernels.h"
 #include "tile_gemm.h"
@@ -1323,15 +1324,58 @@ __global__ void k_gemm_tn_vec(const T* __restrict__ A, const T* __restrict__ B,
   slab_store(wc, acc, C, r0, n0, K, N);
 }
 
+// Where a split reduce puts its result. Elements [0, n0) go to out0 and
+// [n0, n) to out1 (a caller without a second destination passes n0 = n), so a
+// gradient whose rows belong to two parameters (conv dw rows, then the db
+// row) lands in both .grad buffers from the one reduce. acc: the fp32 sum is
+// added to the value already at the destination and rounded once. Neither
+// changes the order in which the slabs are summed.
 template <typename OUT>
-__global__ void k_splitk_reduce(const float* __restrict__ ws,
-                                OUT* __restrict__ out, int z, int64_t n) {
+struct SplitDst {
+  OUT* out0;
+  OUT* out1;
+  int64_t n0;   // in the kernel's own unit: elements, or groups of 4
+  int acc;
+  __device__ OUT* at(int64_t i) const {
+    return i < n0 ? out0 + i : out1 + (i - n0);
+  }
+  // group of 4 elements, 4 * sizeof(OUT) aligned at either destination
+  __device__ OUT* at4(int64_t i4) const {
+    return i4 < n0 ? out0 + 4 * i4 : out1 + 4 * (i4 - n0);
+  }
+};
+
+template <typename OUT>
+__device__ inline void split_store4(const SplitDst<OUT>& d, int64_t i4,
+                                    float r0, float r1, float r2, float r3) {
+  struct alignas(4 * sizeof(OUT)) O4 { OUT e[4]; };
+  O4* p = (O4*)d.at4(i4);
+  if (d.acc) {
+    O4 g = *p;
+    r0 += VecIO<OUT>::to_f32(g.e[0]);
+    r1 += VecIO<OUT>::to_f32(g.e[1]);
+    r2 += VecIO<OUT>::to_f32(g.e[2]);
+    r3 += VecIO<OUT>::to_f32(g.e[3]);
+  }
+  O4 o;
+  o.e[0] = VecIO<OUT>::from_f32(r0);
+  o.e[1] = VecIO<OUT>::from_f32(r1);
+  o.e[2] = VecIO<OUT>::from_f32(r2);
+  o.e[3] = VecIO<OUT>::from_f32(r3);
+  *p = o;
+}
+
+template <typename OUT>
+__global__ void k_splitk_reduce(const float* __restrict__ ws, SplitDst<OUT> d,
+                                int z, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
     float acc = 0.0f;
     for (int s = 0; s < z; ++s) acc += ws[(int64_t)s * n + i];
-    out[i] = VecIO<OUT>::from_f32(acc);
+    OUT* o = d.at(i);
+    if (d.acc) acc += VecIO<OUT>::to_f32(*o);
+    *o = VecIO<OUT>::from_f32(acc);
   }
 }
 
@@ -1340,7 +1384,7 @@ __global__ void k_splitk_reduce(const float* __restrict__ ws,
 // 16B loads x 4-deep MLP reach the HBM roofline.
 template <typename OUT>
 __global__ void k_splitk_reduce4(const float4* __restrict__ ws,
-                                 OUT* __restrict__ out, int z, int64_t n4) {
+                                 SplitDst<OUT> d, int z, int64_t n4) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n4; i += stride) {
@@ -1360,15 +1404,9 @@ __global__ void k_splitk_reduce4(const float4* __restrict__ ws,
       float4 v = ws[(int64_t)s * n4 + i];
       a0.x += v.x; a0.y += v.y; a0.z += v.z; a0.w += v.w;
     }
-    float r[4];
-    r[0] = (a0.x + a1.x) + (a2.x + a3.x);
-    r[1] = (a0.y + a1.y) + (a2.y + a3.y);
-    r[2] = (a0.z + a1.z) + (a2.z + a3.z);
-    r[3] = (a0.w + a1.w) + (a2.w + a3.w);
-    struct alignas(4 * sizeof(OUT)) O4 { OUT e[4]; } o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.e[j] = VecIO<OUT>::from_f32(r[j]);
-    ((O4*)out)[i] = o;
+    split_store4(d, i, (a0.x + a1.x) + (a2.x + a3.x),
+                 (a0.y + a1.y) + (a2.y + a3.y), (a0.z + a1.z) + (a2.z + a3.z),
+                 (a0.w + a1.w) + (a2.w + a3.w));
   }
 }
 
@@ -1377,8 +1415,8 @@ __global__ void k_splitk_reduce4(const float4* __restrict__ ws,
 // one serial z-chain per thread. Here 256/CPB thread-rows split z per
 // column, then an LDS tree folds the rows — same shape as k_slab_fin.
 template <typename OUT, int CPB>
-__global__ void k_splitk_fold(const float4* __restrict__ ws,
-                              OUT* __restrict__ out, int z, int64_t n4) {
+__global__ void k_splitk_fold(const float4* __restrict__ ws, SplitDst<OUT> d,
+                              int z, int64_t n4) {
   constexpr int RPB = 256 / CPB;
   __shared__ float4 sh[256];
   const int cl = threadIdx.x % CPB;
@@ -1403,22 +1441,17 @@ __global__ void k_splitk_fold(const float4* __restrict__ ws,
   }
   if (r == 0 && c < n4) {
     float4 m = sh[cl];
-    struct alignas(4 * sizeof(OUT)) O4 { OUT e[4]; } o;
-    o.e[0] = VecIO<OUT>::from_f32(m.x);
-    o.e[1] = VecIO<OUT>::from_f32(m.y);
-    o.e[2] = VecIO<OUT>::from_f32(m.z);
-    o.e[3] = VecIO<OUT>::from_f32(m.w);
-    ((O4*)out)[c] = o;
+    split_store4(d, c, m.x, m.y, m.z, m.w);
   }
 }
 
 template <typename OUT>
-static void splitk_fold_launch(const float4* ws, OUT* out, int z, int64_t n4,
-                               hipStream_t s, int64_t n4_shape) {
+static void splitk_fold_launch(const float4* ws, SplitDst<OUT> d, int z,
+                               int64_t n4, hipStream_t s, int64_t n4_shape) {
 #define FOLD_CASE(CPB)                                                    \
   hipLaunchKernelGGL((k_splitk_fold<OUT, CPB>),                           \
                      dim3((unsigned)((n4 + CPB - 1) / CPB)), dim3(256), 0, \
-                     s, ws, out, z, n4)
+                     s, ws, d, z, n4)
   if (n4_shape >= 128 * 32) FOLD_CASE(32);
   else if (n4_shape >= 128 * 16) FOLD_CASE(16);
   else if (n4_shape >= 128 * 8) FOLD_CASE(8);
@@ -1428,27 +1461,52 @@ static void splitk_fold_launch(const float4* ws, OUT* out, int z, int64_t n4,
 #undef FOLD_CASE
 }
 
+// Whether splitk_reduce_launch can split n elements at n0 between these two
+// destinations: always on the scalar kernel (n % 4 != 0); the float4 kernels
+// need the boundary on a group of 4 and both destinations aligned to 4
+// elements of out_dt. A caller that gets false reduces into one tensor as
+// before and copies.
+bool splitk_reduce_can_split(int64_t n, int64_t n0, const void* out0,
+                             const void* out1, DT out_dt) {
+  if ((n & 3) != 0) return true;
+  const uintptr_t al = (out_dt == DT::F32 ? 16 : 8) - 1;
+  return (n0 & 3) == 0 && ((uintptr_t)out0 & al) == 0 &&
+         ((uintptr_t)out1 & al) == 0;
+}
+
 // n_shape (default n): the element count the kernel and its fold width are
 // chosen for. A caller that appends rows to an output passes the original
 // size, so the original elements keep their summation order bit for bit.
+// out1 / n0 / accumulate: see SplitDst (out1 == nullptr: everything to out).
 void splitk_reduce_launch(const float* ws, void* out, DT out_dt, int z,
-                          int64_t n, hipStream_t s, int64_t n_shape) {
+                          int64_t n, hipStream_t s, int64_t n_shape,
+                          void* out1, int64_t n0, bool accumulate) {
   if (n_shape <= 0) n_shape = n;
+  if (!out1) n0 = n;
+  // the float4 kernels cannot split anywhere: a caller that did not ask
+  // splitk_reduce_can_split first must not get misplaced elements
+  if (out1 && (n0 < 0 || n0 > n ||
+               !splitk_reduce_can_split(n, n0, out, out1, out_dt)))
+    throw std::invalid_argument(
+        "splitk_reduce_launch: the two destinations cannot be split here "
+        "(boundary or pointer off a group of 4); see splitk_reduce_can_split");
   dispatch_dt(out_dt, [&](auto tag) {
     using OUT = typename decltype(tag)::type;
+    const int acc = accumulate ? 1 : 0;
+    const SplitDst<OUT> d1{(OUT*)out, (OUT*)out1, n0, acc};
+    const SplitDst<OUT> d4{(OUT*)out, (OUT*)out1, n0 >> 2, acc};
     if ((n & 3) == 0 && (n_shape & 3) == 0 && n_shape < 4 * 32768 && z >= 8) {
       // small output x deep z: parallelize over z (see k_splitk_fold)
-      splitk_fold_launch((const float4*)ws, (OUT*)out, z, n >> 2, s,
-                         n_shape >> 2);
+      splitk_fold_launch((const float4*)ws, d4, z, n >> 2, s, n_shape >> 2);
     } else if ((n & 3) == 0) {
       int64_t n4 = n >> 2;
       int blocks = (int)std::min<int64_t>((n4 + 255) / 256, (int64_t)2048);
       hipLaunchKernelGGL(k_splitk_reduce4<OUT>, dim3(blocks), dim3(256), 0, s,
-                         (const float4*)ws, (OUT*)out, z, n4);
+                         (const float4*)ws, d4, z, n4);
     } else {
       int blocks = (int)std::min<int64_t>((n + 255) / 256, (int64_t)2048);
       hipLaunchKernelGGL(k_splitk_reduce<OUT>, dim3(blocks), dim3(256), 0, s,
-                         ws, (OUT*)out, z, n);
+                         ws, d1, z, n);
     }
   });
 }

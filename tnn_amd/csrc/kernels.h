@@ -51,8 +51,11 @@ void dropout_bwd_launch(DT dt, const void* dy, const uint8_t* mask, void* dx,
 int colsum_ws_slices(DT dt, const void* x, int64_t rows, int64_t cols);
 void colsum_launch(DT dt, const void* x, void* out_f32, float* ws,
                    int rslices, int64_t rows, int64_t cols, hipStream_t s);
+// d0 / d1 (optional): columns [0, c2/2) are also written to d0 and
+// [c2/2, c2) to d1, or added to them (accumulate)
 void slab_fin_launch(const float* ws, float* out, int slices, int c2,
-                     hipStream_t s);
+                     hipStream_t s, float* d0 = nullptr, float* d1 = nullptr,
+                     bool accumulate = false);
 void cast_f32_launch(DT dt_out, const float* x, void* y, int64_t n,
                      hipStream_t s);
 
@@ -96,8 +99,14 @@ int gemm_tn_zsplits(int M, int N, int K);
 void gemm_tn_launch(DT dt, const void* a, const void* b, void* c_out,
                     DT out_dt, float* ws, int z, const void* zero16, int M,
                     int N, int K, hipStream_t s);
+// out1 != nullptr: elements [0, n0) go to out, [n0, n) to out1; accumulate:
+// added (in fp32, rounded once) to what the destination holds
 void splitk_reduce_launch(const float* ws, void* out, DT out_dt, int z,
-                          int64_t n, hipStream_t s, int64_t n_shape = 0);
+                          int64_t n, hipStream_t s, int64_t n_shape = 0,
+                          void* out1 = nullptr, int64_t n0 = 0,
+                          bool accumulate = false);
+bool splitk_reduce_can_split(int64_t n, int64_t n0, const void* out0,
+                             const void* out1, DT out_dt);
 void mfma_selftest_launch(const void* a_bf16, const void* b_bf16, float* d,
                           hipStream_t s);
 void mfma_selftest_f32_launch(const float* a, const float* b, float* d,
@@ -145,6 +154,9 @@ struct ConvShape {
 bool conv2d_fwd_wants_db(DT dt, const void* x, const ConvShape& cs);
 void transpose_w_fwd_launch(DT dt, const void* w, void* w_t2, int KHW, int Cin,
                             int Cout, hipStream_t s);
+// stats (optional, w_t2 routes only): fused-statistics partials
+// [conv2d_fwd_stats_rows][2][Cout], every element written (no zero-init)
+int conv2d_fwd_stats_rows(const ConvShape& cs);
 void conv2d_fwd_launch(DT dt, const void* x, const void* w, const void* w_t2,
                        const void* bias, void* y, const void* zero16,
                        float* stats, const ConvShape& cs, bool relu,
@@ -166,9 +178,16 @@ const char* conv2d_wgrad_route(DT dt, const void* x, const void* dy,
                                const ConvShape& cs);
 int conv2d_wgrad_zsplits(DT dt, const void* x, const void* dy,
                          const ConvShape& cs);
+// gradient sink of a wgrad launch: the reduce writes dw ([Kout][Cout]) to
+// dw_out and the bias row to db_out, or adds to them (accumulate)
+struct WgradSink {
+  void* db_out = nullptr;
+  bool accumulate = false;
+};
 void conv2d_wgrad_launch(DT dt, const void* x, const void* dy, void* dw_out,
                          DT out_dt, float* ws, int z, const void* zero16,
-                         const ConvShape& cs, bool bias, hipStream_t s);
+                         const ConvShape& cs, bool bias, hipStream_t s,
+                         const WgradSink* sink = nullptr);
 void transpose_w_launch(DT dt, const void* w, void* w_t, int KH, int KW,
                         int Cin, int Cout, hipStream_t s);
 
@@ -181,6 +200,12 @@ void bn_finalize_launch(const float* sum, const float* sumsq, float* mean,
                         float* invstd, float* rmean, float* rvar,
                         float momentum, int64_t rows, int cols, float eps,
                         hipStream_t s);
+// the same from [slices][2][cols] partials (the conv epilogue's): folds the
+// slices in k_slab_fin's order and finalizes, one launch
+void bn_finalize_fold_launch(const float* partials, int slices, float* mean,
+                             float* invstd, float* rmean, float* rvar,
+                             float momentum, int64_t rows, int cols, float eps,
+                             hipStream_t s);
 void bn_apply_launch(DT dt, const void* x, const float* mean,
                      const float* invstd, const float* gamma, const float* beta,
                      void* y, int64_t rows, int cols, bool relu, hipStream_t s);
@@ -195,10 +220,14 @@ void bn_infer_launch(DT dt, const void* x, const float* rmean,
                      hipStream_t s);
 int64_t bn_bwd_ws_floats(DT dt, const void* x, const void* dy, int64_t rows,
                          int cols);
+// dgamma_out / dbeta_out (slab path only, ws != nullptr): the finalize also
+// writes sum_dy_xhat / sum_dy there, or adds to them (accumulate)
 void bn_bwd_reduce_launch(DT dt, const void* x, const void* dy, const void* y_relu,
                           const float* mean, const float* invstd, float* sum_dy,
                           float* sum_dy_xhat, float* ws, int64_t rows, int cols,
-                          float dy_scale, hipStream_t s);
+                          float dy_scale, hipStream_t s,
+                          float* dgamma_out = nullptr,
+                          float* dbeta_out = nullptr, bool accumulate = false);
 void bn_bwd_apply_launch(DT dt, const void* x, const void* dy, const void* y_relu,
                          const float* mean, const float* invstd,
                          const float* gamma, const float* sum_dy,

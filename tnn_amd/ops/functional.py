@@ -56,6 +56,79 @@ def set_graph_seed_ctr(t: Optional[torch.Tensor]):
     _graph_ctr = t
 
 
+# Gradient sinks: a training step that owns fixed gradient buffers (the
+# per-dtype slabs of GraphedTrainStep) registers them here, and the conv and
+# batch-norm backwards then have their reduce kernels write dw / db / dgamma /
+# dbeta straight into the buffer and hand autograd None for that input --
+# instead of returning a fresh tensor that autograd adds to the zeroed buffer
+# with one more launch per parameter. With no registry active (eager training,
+# the pipeline engine, DDP) nothing changes.
+class GradSinks:
+    """Parameter -> gradient buffer, plus the per-step "written" marks.
+
+    The first write of a step overwrites the buffer, any later write in the
+    same step accumulates (a layer applied twice); ``begin_step`` clears the
+    marks. Keys are the parameters' ``data_ptr()``: a backward sees the tensor
+    that reached its forward, which is the parameter or an alias of it."""
+
+    def __init__(self, params=()):
+        self._buf = {}
+        self.written = set()
+        for p in params:
+            self.register(p, p.grad)
+
+    def register(self, param: torch.Tensor, buf: torch.Tensor):
+        if (buf is None or buf.shape != param.shape or buf.dtype != param.dtype
+                or buf.device != param.device or not buf.is_contiguous()):
+            raise ValueError("gradient sink must be a contiguous buffer of the "
+                             "parameter's shape, dtype and device")
+        self._buf[param.data_ptr()] = buf
+
+    def begin_step(self):
+        self.written.clear()
+
+    def get(self, key, like: Optional[torch.Tensor] = None):
+        """The buffer registered under ``key`` (None if there is none, or if
+        it does not match the shape and dtype of ``like``)."""
+        buf = self._buf.get(key)
+        if buf is not None and like is not None and (
+                buf.shape != like.shape or buf.dtype != like.dtype):
+            return None
+        return buf
+
+    def claim(self, key) -> bool:
+        """Mark ``key`` written in this step; returns whether the write has
+        to accumulate (it was written before in the same step)."""
+        accumulate = key in self.written
+        self.written.add(key)
+        return accumulate
+
+
+_grad_sinks: Optional[GradSinks] = None
+
+
+def grad_sinks_enabled() -> bool:
+    """``TNN_GRAD_SINK=0`` turns the gradient sinks off."""
+    import os
+    return os.environ.get("TNN_GRAD_SINK", "1") != "0"
+
+
+def set_grad_sinks(sinks: Optional[GradSinks]):
+    global _grad_sinks
+    _grad_sinks = sinks
+
+
+def _sink_key(t: Optional[torch.Tensor]):
+    # recorded in forward, from the tensor as the layer passed it. Only a
+    # contiguous tensor can be the parameter itself: a same-shape view with
+    # other strides (a transposed square weight) shares the pointer but not
+    # the element order, and gets its gradient from autograd
+    if (_grad_sinks is None or t is None or not t.requires_grad
+            or not t.is_contiguous()):
+        return None
+    return t.data_ptr()
+
+
 def _draw_seed() -> int:
     if _graph_ctr is not None:
         import random
@@ -78,15 +151,18 @@ class _Conv2dNHWC(torch.autograd.Function):
         Ci = x.shape[-1]
         V = 8 if x.dtype == torch.bfloat16 else 4
         ctx.cin = Ci
+        ctx.sink_keys = (_sink_key(w), _sink_key(bias))
         if Ci % V != 0 and Ci < V:
             x = F.pad(x, (0, V - Ci))
             w = F.pad(w, (0, 0, 0, V - Ci))
         ctx.want_stats = want_stats
         if want_stats:
-            # fused per-channel sum/sumsq for a following train-mode BN;
-            # stats is empty when the fused kernel is not eligible
-            y, stats = ext.conv2d_fwd_stats(x, w, bias, stride[0], stride[1],
-                                            padding[0], padding[1])
+            # fused per-channel sum/sumsq for a following train-mode BN, as
+            # slab partials [m-tiles, 2, Cout] that bn_fwd_train folds in its
+            # finalize; empty when the fused kernel is not eligible
+            y, stats = ext.conv2d_fwd_partials(x, w, bias, stride[0],
+                                               stride[1], padding[0],
+                                               padding[1])
         else:
             y = ext.conv2d_fwd(x, w, bias, stride[0], stride[1], padding[0],
                                padding[1], fuse_relu)
@@ -94,12 +170,18 @@ class _Conv2dNHWC(torch.autograd.Function):
         ctx.stride, ctx.padding, ctx.fuse_relu = stride, padding, fuse_relu
         ctx.has_bias = bias is not None
         if want_stats:
+            # non-differentiable alone does not keep autograd from filling a
+            # zero [2, Cout] gradient for stats on every backward (one fill
+            # per fused-statistics conv and step, seen in the profiler)
             ctx.mark_non_differentiable(stats)
+            ctx.set_materialize_grads(False)
             return y, stats
         return y
 
     @staticmethod
     def backward(ctx, dy, *unused_stats_grad):
+        if dy is None:  # y unused (grads are not materialized with stats)
+            return None, None, None, None, None, None, None
         x, w, y = ctx.saved_tensors
         ext = _C.ext()
         dy = dy.contiguous()
@@ -112,6 +194,10 @@ class _Conv2dNHWC(torch.autograd.Function):
             if x.shape[-1] != ctx.cin:
                 dx = dx[..., :ctx.cin].contiguous()
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] and _grad_sinks is not None:
+            sunk = _Conv2dNHWC._wgrad_into_sinks(ctx, x, w, dy, want_db)
+            if sunk is not None:
+                return (dx,) + sunk + (None, None, None, None)
         if ctx.needs_input_grad[1]:
             args = (x, dy, w.shape[0], w.shape[1], ctx.stride[0],
                     ctx.stride[1], ctx.padding[0], ctx.padding[1],
@@ -130,6 +216,51 @@ class _Conv2dNHWC(torch.autograd.Function):
             db = ext.colsum(dy.reshape(-1, dy.shape[-1]))
         return dx, dw, db, None, None, None, None
 
+    @staticmethod
+    def _wgrad_into_sinks(ctx, x, w, dy, want_db):
+        """Weight (and bias) gradient through the registered sinks: returns
+        the (dw, db) to hand autograd -- None where the reduce wrote the
+        buffer -- or None when this layer goes the old way. The padded RGB
+        stem keeps dw on the old path (it is sliced out of the padded
+        gradient) but still sinks db."""
+        sinks = _grad_sinks
+        wkey, bkey = ctx.sink_keys
+        padded = x.shape[-1] != ctx.cin
+        dwbuf = dbbuf = None
+        if w.dtype not in (x.dtype, torch.float32):
+            return None
+        if not padded:
+            dwbuf = sinks.get(wkey, w)
+            if dwbuf is None:
+                return None
+        if want_db:
+            dbbuf = sinks.get(bkey, w[0, 0, 0])
+            if dbbuf is None:
+                return None
+        if dwbuf is None and dbbuf is None:
+            return None
+        if (dwbuf is not None and dbbuf is not None
+                and (wkey in sinks.written) != (bkey in sinks.written)):
+            return None  # one reduce, one accumulate flag
+        ext = _C.ext()
+        acc = False
+        if dwbuf is not None:
+            acc = sinks.claim(wkey)
+        if dbbuf is not None:
+            acc = sinks.claim(bkey)
+        dw = None
+        if padded:
+            # accumulate into a scratch dw would read garbage: zero it then
+            dwbuf = (torch.zeros if acc else torch.empty)(
+                w.shape, dtype=w.dtype, device=w.device)
+            dw = dwbuf
+        ext.conv2d_wgrad_into(x, dy, w.shape[0], w.shape[1], ctx.stride[0],
+                              ctx.stride[1], ctx.padding[0], ctx.padding[1],
+                              dwbuf, dbbuf, acc)
+        if padded:
+            dw = dw[:, :, :ctx.cin].contiguous()
+        return dw, None
+
 
 def conv2d_nhwc(
     x: torch.Tensor,
@@ -143,8 +274,10 @@ def conv2d_nhwc(
     """2-D convolution, NHWC activations, ``[KH,KW,Cin,Cout]`` weights.
 
     ``want_stats=True`` (GPU, linear act) additionally returns the fused
-    per-channel (sum, sumsq) for a following train-mode BatchNorm, or None
-    when the fused kernel is not eligible."""
+    per-channel (sum, sumsq) for a following train-mode BatchNorm as slab
+    partials ``[m-tiles, 2, Cout]`` (``batch_norm_act(precomputed=...)``
+    takes them as they are), or None when the fused kernel is not
+    eligible."""
     if _use_hip(x):
         if want_stats:
             y, stats = _Conv2dNHWC.apply(
@@ -171,6 +304,25 @@ def conv2d_nhwc(
 # ---------------------------------------------------------------------------
 
 
+def _bn_sinks(ctx, x, dy) -> dict:
+    """bn_bwd keyword arguments that send dgamma / dbeta to the registered
+    sinks; empty when the layer returns them the old way (no sink for both,
+    one of them not wanted, or the scalar path, which has no finalize)."""
+    sinks = _grad_sinks
+    if sinks is None or not (ctx.needs_input_grad[1]
+                             and ctx.needs_input_grad[2]):
+        return {}
+    gkey, bkey = ctx.sink_keys
+    gbuf, bbuf = sinks.get(gkey), sinks.get(bkey)
+    if (gbuf is None or bbuf is None or gbuf.dtype != torch.float32
+            or bbuf.dtype != torch.float32
+            or (gkey in sinks.written) != (bkey in sinks.written)
+            or not _C.ext().bn_bwd_takes_sink(x, dy)):
+        return {}
+    sinks.claim(gkey)
+    return dict(dgamma_out=gbuf, dbeta_out=bbuf, accumulate=sinks.claim(bkey))
+
+
 class _BatchNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum,
@@ -185,19 +337,29 @@ class _BatchNormAct(torch.autograd.Function):
                                            dropout_p, seed, precomp, ctr)
         save_y = y if (relu or dropout_p > 0.0) else None
         ctx.save_for_backward(x, gamma, mean, invstd, save_y)
+        ctx.sink_keys = (_sink_key(gamma), _sink_key(beta))
         ctx.relu = relu or dropout_p > 0.0
         ctx.dy_scale = 1.0 / (1.0 - dropout_p) if dropout_p > 0.0 else 1.0
-        # without this autograd materializes zero grads for mean/invstd on
-        # every backward (2 fill launches per BN per step)
+        # mean/invstd carry no gradient; without set_materialize_grads(False)
+        # autograd still fills a zero grad for each on every backward (2 fill
+        # launches per BN per step, seen in the profiler)
         ctx.mark_non_differentiable(mean, invstd)
+        ctx.set_materialize_grads(False)
         return y, mean, invstd
 
     @staticmethod
     def backward(ctx, dy, _dmean, _dinvstd):
+        if dy is None:
+            return (None,) * 12
         x, gamma, mean, invstd, y = ctx.saved_tensors
         ext = _C.ext()
-        dx, dgamma, dbeta = ext.bn_bwd(x, dy.contiguous(), gamma, mean, invstd,
-                                       y if ctx.relu else None, ctx.dy_scale)
+        dy = dy.contiguous()
+        sink = _bn_sinks(ctx, x, dy)
+        dx, dgamma, dbeta = ext.bn_bwd(x, dy, gamma, mean, invstd,
+                                       y if ctx.relu else None, ctx.dy_scale,
+                                       **sink)
+        if sink:
+            dgamma = dbeta = None
         return (dx, dgamma, dbeta, None, None, None, None, None, None, None,
                 None, None)
 
@@ -217,6 +379,7 @@ class _BatchNormActRes(torch.autograd.Function):
                                            dropout_p, seed, precomp, ctr)
         save_y = y if (relu or dropout_p > 0.0) else None
         ctx.save_for_backward(x, gamma, mean, invstd, save_y)
+        ctx.sink_keys = (_sink_key(gamma), _sink_key(beta))
         ctx.relu = relu or dropout_p > 0.0
         ctx.dy_scale = 1.0 / (1.0 - dropout_p) if dropout_p > 0.0 else 1.0
         ctx.mark_non_differentiable(mean, invstd)
@@ -232,9 +395,13 @@ class _BatchNormActRes(torch.autograd.Function):
                     None, None, None)
         if dres is not None:
             dres = dres.contiguous()
-        dx, dgamma, dbeta = ext.bn_bwd(x, dy.contiguous(), gamma, mean,
-                                       invstd, y if ctx.relu else None,
-                                       ctx.dy_scale, resid=dres)
+        dy = dy.contiguous()
+        sink = _bn_sinks(ctx, x, dy)
+        dx, dgamma, dbeta = ext.bn_bwd(x, dy, gamma, mean, invstd,
+                                       y if ctx.relu else None, ctx.dy_scale,
+                                       resid=dres, **sink)
+        if sink:
+            dgamma = dbeta = None
         return (dx, dgamma, dbeta, None, None, None, None, None, None, None,
                 None, None)
 
