@@ -16,9 +16,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tnn_amd import models
 from tnn_amd.nn import CrossEntropyLoss, AdamW
 from tnn_amd.nn.layer import cast_compute_dtype
-from tnn_amd.models.generate import (DecodeSession, generate,
+from tnn_amd.models.generate import (BatchedDecoder, DecodeSession, generate,
                                       generate_batch, generate_cached,
-                                      generate_graphed)
+                                      generate_graphed, generate_speculative)
 
 
 def main():
@@ -36,6 +36,14 @@ def main():
                         "contexts of 768 (DecodeSession) against "
                         "generate_batch on the concatenated prompts; wants "
                         "--seq-len 1024")
+    p.add_argument("--speculative", action="store_true",
+                   help="time greedy speculative decode (generate_speculative"
+                        ", --draft proposes --draft-k tokens per round) on 8 "
+                        "prompts of 3/4 seq-len: the target's single-token "
+                        "step, the verify step, the draft's time per round "
+                        "and tokens per second against generate_batch")
+    p.add_argument("--draft", default="flash_gpt2_small")
+    p.add_argument("--draft-k", type=int, default=4)
     p.add_argument("--train", action="store_true", default=True)
     p.add_argument("--graph", action="store_true",
                    help="also time the hipGraph-captured whole train step")
@@ -140,6 +148,13 @@ def main():
               f"{n / dt / args.decode_batch:.2f} tok/s per sequence")
     if args.second_turn:
         second_turn(model, dev, args.seq_len, args.decode_tokens)
+    if args.speculative:
+        draft = models.create_model(args.draft)
+        if dev.type == "cuda":
+            cast_compute_dtype(draft, torch.bfloat16)
+        draft.to(dev).eval()
+        speculative(model, draft, args.model, args.draft, dev, args.seq_len,
+                    args.decode_tokens, args.draft_k)
 
 
 def second_turn(model, dev, seq_len, n_tokens, rows=8, ctx_len=768, turn=64):
@@ -188,6 +203,131 @@ def second_turn(model, dev, seq_len, n_tokens, rows=8, ctx_len=768, turn=64):
                   f" | generate_batch {res['batch', tag][0] * 1e3:.1f} ms")
     finally:
         sess.close()
+
+
+def speculative(model, draft, mname, dname, dev, seq_len, n_tokens, k,
+                rows=8, iters=30):
+    """Greedy speculative decode: step times of its three parts on live
+    caches of ``rows`` contexts of 3/4 seq_len, then whole calls against
+    generate_batch. Single-token steps are timed as captured graphs (what
+    both loops replay), the verify step eagerly (what the loop runs); every
+    window is ``iters`` calls ending in a synchronise, after a warm-up."""
+    from tnn_amd.ops import sample_logits
+    ctx_len = seq_len * 3 // 4
+    g = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, 50257, (ctx_len,), generator=g).tolist()
+               for _ in range(rows)]
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+
+    def window(fn, n=iters, warm=5):
+        for _ in range(warm):
+            fn()
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        sync()
+        return (time.perf_counter() - t0) / n
+
+    def step_time(m, per_call):
+        """one single-token step of the decode loops, graph-replayed
+        ``per_call`` times from the same positions"""
+        dec = BatchedDecoder(m, seq_len, dev)
+        try:
+            dec.prefill(prompts)
+            tok = torch.zeros(rows, 1, dtype=torch.int64, device=dev)
+            saved = dec.pos.clone()
+
+            def step():
+                nxt = sample_logits(dec.forward_token(tok), temperature=0)
+                tok.copy_(nxt.reshape(rows, 1))
+                dec.advance()
+
+            run = step
+            if dev.type == "cuda":
+                stream = torch.cuda.Stream()
+                stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(stream):
+                    for _ in range(2):
+                        step()
+                torch.cuda.current_stream().wait_stream(stream)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    step()
+                run = graph.replay
+
+            def call():
+                dec.pos.copy_(saved)
+                for _ in range(per_call):
+                    run()
+            return window(call)
+        finally:
+            dec.close()
+
+    def verify_time(split):
+        dec = BatchedDecoder(model, seq_len, dev)
+        try:
+            dec.prefill(prompts)
+            x = torch.randint(0, 50257, (rows, k + 1), generator=g).to(dev)
+            n = torch.full((rows,), k + 1, dtype=torch.int64, device=dev)
+            saved = dec.pos.clone()
+
+            def call():
+                dec.pos.copy_(saved)
+                if split:
+                    dec._verify(x, n)
+                else:
+                    lg = dec._extend_logits(x, n, 0)
+                    sample_logits(lg.reshape(rows * (k + 1), -1),
+                                  temperature=0)
+            return window(call)
+        finally:
+            dec.close()
+
+    with torch.no_grad():
+        t_step = step_time(model, 1)
+        t_draft = step_time(draft, k + 1)
+        t_ver, t_ver0 = verify_time(True), verify_time(False)
+    heads = {a.num_heads for a in model.modules() if hasattr(a, "num_heads")}
+    print(f"speculative [{mname} <- {dname}, k={k}, {rows} x {ctx_len}]: "
+          f"target step {t_step * 1e3:.3f} ms | verify T={k + 1} "
+          f"{t_ver * 1e3:.3f} ms (unsplit attention {t_ver0 * 1e3:.3f} ms, "
+          f"heads {sorted(heads)}) | draft round ({k + 1} steps) "
+          f"{t_draft * 1e3:.3f} ms")
+    round_t = t_draft + t_ver
+    print(f"speculative: round / step = {round_t / t_step:.2f}, verify / "
+          f"step = {t_ver / t_step:.2f}, draft step / step = "
+          f"{t_draft / (k + 1) / t_step:.2f}; break-even at "
+          f"{round_t / t_step - 1:.2f} accepted drafts per round of {k} "
+          f"(device time only)")
+    for name, fn in (
+            ("generate_batch", lambda: generate_batch(
+                model, prompts, max_new_tokens=n_tokens, seq_len=seq_len,
+                device=dev, eot_token=None)),
+            ("generate_speculative", lambda: generate_speculative(
+                model, draft, prompts, max_new_tokens=n_tokens, k=k,
+                seq_len=seq_len, device=dev, eot_token=None,
+                return_stats=True))):
+        for _ in range(2):   # the second call is the steady-state figure
+            sync()
+            t0 = time.perf_counter()
+            out = fn()
+            sync()
+            dt = time.perf_counter() - t0
+        stats = None
+        if isinstance(out, tuple):
+            out, stats = out
+        n = sum(len(o) - len(q) for o, q in zip(out, prompts))
+        line = (f"decode [{name} x{rows}]: {n} tokens in {dt:.3f}s = "
+                f"{n / dt:.1f} tok/s")
+        if stats:
+            acc, dr = sum(stats["accepted"]), sum(stats["drafted"])
+            line += (f"; {stats['rounds']} rounds, accepted {acc} of {dr} "
+                     f"drafts ({acc / max(dr, 1):.3f})")
+        print(line)
 
 
 if __name__ == "__main__":

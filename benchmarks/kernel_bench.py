@@ -156,6 +156,55 @@ def bench_attn_extend():
                         best[name] = min(secs, best.get(name, secs))
             for name, secs in best.items():
                 report(name, f"B{B} H{H} D{D} pos{pos} T{T}", secs, fl)
+        # split-KV rows (verify-step shapes, T <= 16): kv_splits = 0 is the
+        # unsplit kernel above; "auto" names what attn_extend_splits picks
+        for pos, T in [(1016, 8), (1008, 16), (960, 16), (512, 8), (64, 8),
+                       (0, 8)]:
+            qkv = torch.randn(B, T, 3 * H * D, dtype=torch.bfloat16,
+                              device=DEV)
+            q = qkv[..., :H * D].view(B, T, H, D).transpose(1, 2)
+            pos_t = torch.full((B,), pos, dtype=torch.int64, device=DEV)
+            routes = {
+                ns: (lambda ns=ns: ext.attn_extend(q, kc, vc, pos_t, None,
+                                                   D ** -0.5, ns))
+                for ns in (0, 1, 2, 4, 8, 16)}
+            fl = 4.0 * B * H * D * (T * pos + T * (T + 1) / 2)
+            best = {}
+            with torch.no_grad():
+                for _ in range(2):
+                    for ns, fn in routes.items():
+                        secs = timeit(fn)
+                        best[ns] = min(secs, best.get(ns, secs))
+            auto = ext.attn_extend_splits(B * H, cap, T)
+            for ns, secs in best.items():
+                report(f"attn_extend ns{ns}" + ("*" if ns == auto else ""),
+                       f"B{B} H{H} D{D} pos{pos} T{T}", secs, fl)
+        print(f"(* = automatic split count for B*H={B * H} cap={cap})")
+
+
+def bench_attn_extend_splits():
+    """Split counts of the split-KV extend kernel away from the B=8 head
+    configurations of bench_attn_extend: few and many (b, h) rows, a short
+    and a long cache. What the table above attn_ext_splits rests on; same
+    protocol (routes in turn, twice, better round)."""
+    D = 64
+    for B, H, cap in [(1, 12, 1024), (1, 20, 1024), (4, 8, 1024),
+                      (4, 2, 320), (16, 12, 1024), (16, 20, 1024),
+                      (8, 12, 4096)]:
+        kc = torch.randn(B, H, cap, D, dtype=torch.bfloat16, device=DEV)
+        vc = torch.randn_like(kc)
+        for pos, T in [(cap - 8, 8), (cap // 2, 8), (cap - 16, 5)]:
+            q = torch.randn(B, H, T, D, dtype=torch.bfloat16, device=DEV)
+            pos_t = torch.full((B,), pos, dtype=torch.int64, device=DEV)
+            best = {}
+            for _ in range(2):
+                for ns in (0, 2, 3, 4, 6, 8, 16):
+                    secs = timeit(lambda: ext.attn_extend(
+                        q, kc, vc, pos_t, None, D ** -0.5, ns))
+                    best[ns] = min(secs, best.get(ns, secs))
+            auto = ext.attn_extend_splits(B * H, cap, T)
+            print(f"attn_extend BH{B * H} cap{cap} pos{pos} T{T} auto={auto} us:"
+                  + "".join(f" ns{n}={s * 1e6:.1f}" for n, s in best.items()))
 
 
 def bench_bmm():
@@ -292,7 +341,8 @@ def bench_gradnorm():
 
 ALL = {"gemm": bench_gemm, "conv": bench_conv, "bn": bench_bn,
        "colsum": bench_colsum, "ce": bench_ce, "attn": bench_attn,
-       "attn_extend": bench_attn_extend, "bmm": bench_bmm,
+       "attn_extend": bench_attn_extend,
+       "attn_extend_splits": bench_attn_extend_splits, "bmm": bench_bmm,
        "softmax": bench_softmax, "ln": bench_ln,
        "gn": bench_gn, "decode": bench_decode, "skinny": bench_skinny,
        "sample": bench_sample, "gradnorm": bench_gradnorm}

@@ -9,6 +9,9 @@
 ``--batch N`` decodes N prompts together through ``generate_batch`` (one
 hipGraph-captured step for all rows on GPU); ``--top-k`` / ``--top-p`` /
 ``--temperature`` / ``--seed`` switch it from greedy to on-device sampling.
+``--draft MODEL --draft-k K`` decodes greedily through
+``generate_speculative``: MODEL drafts K tokens per round, ``--model``
+verifies them in one forward (same tokens as the plain greedy decode).
 
 Without a vocab/snapshot this runs with random weights and raw token ids —
 the compute path (embedding -> N gpt blocks -> ln_f -> head, full-sequence
@@ -26,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tnn_amd import models
 from tnn_amd.data import Tokenizer
-from tnn_amd.models.generate import generate, generate_batch, generate_cached
+from tnn_amd.models.generate import (generate, generate_batch,
+                                      generate_cached, generate_speculative)
 from tnn_amd.nn.layer import cast_compute_dtype
 from tnn_amd.utils.checkpoint import load_model
 
@@ -48,6 +52,11 @@ def main():
     p.add_argument("--top-p", type=float, default=1.0)
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--draft", default=None,
+                   help="draft model for greedy speculative decode "
+                        "(generate_speculative)")
+    p.add_argument("--draft-k", type=int, default=4,
+                   help="draft tokens per round, 1..15")
     args = p.parse_args()
 
     model = (load_model(args.snapshot) if args.snapshot
@@ -61,6 +70,30 @@ def main():
     prompt_ids = tok.encode(args.prompt) if tok else list(range(10))
 
     sampled = (args.top_k > 0 or args.top_p < 1.0 or args.temperature != 1.0)
+    if args.draft:
+        if sampled:
+            p.error("--draft is greedy only")
+        draft = models.create_model(args.draft)
+        if args.bf16:
+            cast_compute_dtype(draft, torch.bfloat16)
+        draft.to(dev)
+        n = max(args.batch, 1)
+        prompts = [prompt_ids + prompt_ids[:b % len(prompt_ids)]
+                   for b in range(n)]
+        t0 = time.perf_counter()
+        outs, stats = generate_speculative(
+            model, draft, prompts, max_new_tokens=args.tokens,
+            k=args.draft_k, seq_len=args.seq_len, device=dev,
+            eot_token=50256 if tok else None, return_stats=True)
+        dt = time.perf_counter() - t0
+        n_new = sum(len(o) - len(q) for o, q in zip(outs, prompts))
+        acc, dr = sum(stats["accepted"]), sum(stats["drafted"])
+        print(f"{n_new} tokens in {dt:.2f}s ({n_new / dt:.2f} tok/s aggregate "
+              f"over {n} sequences, speculative k={args.draft_k}: "
+              f"{stats['rounds']} rounds, {acc} of {dr} drafts accepted)")
+        for o in outs:
+            print(tok.decode(o) if tok else o)
+        return
     if args.batch > 0 or sampled:
         # the same prompt with a ragged tail of extra tokens per row
         n = max(args.batch, 1)

@@ -559,6 +559,209 @@ __global__ void k_attn_ext(const bf16* __restrict__ Q, const bf16* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// Split-KV extend attention (inference, T <= 16): the one-wave form of
+// k_attn_ext with the live prefix divided among gridDim.x blocks, for a
+// verify step's few query rows on a long prefix, where B*H one-wave blocks
+// alone leave most CUs idle and each walks the whole prefix.
+//   * grid (NS, B*H), 64 threads; the split is over the LIVE tiles, not the
+//     capacity: ntiles = ceil((p0 + n) / BKV), per = ceil(ntiles / NS),
+//     split s walks tiles [s * per, min((s + 1) * per, ntiles)). Everything
+//     here depends on blockIdx and block-uniform device scalars, so the
+//     barriers stay legal;
+//   * a split without tiles (and every split of a row with n == 0) stores
+//     m = -inf, l = 0 and leaves before its first barrier; its po rows stay
+//     unwritten and k_attn_ext_fin never reads them;
+//   * each split stores unnormalised fp32 partials po[bh][s][16][D] and
+//     ml[bh][s][16][{m, l}] with plain stores: no zero-init, no atomics, so
+//     two calls give the same bits;
+//   * q strides, zero page, pos / n_new clamps, causal and dead-slot rules
+//     are k_attn_ext's.
+template <int D>
+__launch_bounds__(64)
+__global__ void k_attn_ext_split(const bf16* __restrict__ Q,
+                                 const bf16* __restrict__ K,
+                                 const bf16* __restrict__ V,
+                                 float* __restrict__ po, float* __restrict__ ml,
+                                 const int64_t* __restrict__ pos,
+                                 const int64_t* __restrict__ n_new,
+                                 const bf16* __restrict__ zero16, int T,
+                                 int cap, int H, int64_t q_rs, int64_t q_hs,
+                                 int64_t q_bs, float scale) {
+  constexpr int FN = BKV / 16;
+  constexpr int FO = D / 16;
+  __shared__ alignas(16) bf16 q_lds[16 * D];
+  __shared__ alignas(16) bf16 k_lds[2][BKV * D];
+  __shared__ alignas(16) bf16 vt_lds[2][(D + 16) * BKV];
+  bf16* p_lds = q_lds;  // aliased after the Q fragments are hoisted
+
+  const int NS = gridDim.x, split = blockIdx.x;
+  const int64_t bh = blockIdx.y;
+  const int64_t b = bh / H, h = bh % H;
+  const int p0 = (int)min(max(pos[b], (int64_t)0), (int64_t)cap);
+  const int n = (int)min(max(n_new ? n_new[b] : (int64_t)T, (int64_t)0),
+                         (int64_t)min(T, cap - p0));
+  const int kv_len = p0 + n;
+  const int ntiles = n > 0 ? (kv_len + BKV - 1) / BKV : 0;
+  const int per = (ntiles + NS - 1) / NS;
+  const int t0 = split * per;
+  const int t1 = min(t0 + per, ntiles);
+  const int lane = threadIdx.x;
+  const int cr = (lane >> 4) * 4;
+  const int cc = lane & 15;
+  float* pob = po + (bh * NS + split) * 16 * D;
+  float* mlb = ml + (bh * NS + split) * 16 * 2;
+
+  if (t0 >= t1) {  // nothing to walk
+    if (lane < 16) {
+      mlb[lane * 2] = -INFINITY;
+      mlb[lane * 2 + 1] = 0.0f;
+    }
+    return;
+  }
+
+  const bf16* q = Q + b * q_bs + h * q_hs;
+  const bf16* k = K + bh * cap * D;
+  const bf16* v = V + bh * cap * D;
+
+  stage_tile<16, D, 1>(q, q_lds, n, zero16, q_rs);
+  for (int i = lane; i < 16 * BKV; i += 64) {
+    const int rr = i / BKV, col = i % BKV;
+    const bf16 val = f2bf(rr == 0 ? 1.0f : 0.0f);
+    vt_lds[0][aoff<bf16, BKV>(D + rr, col)] = val;
+    vt_lds[1][aoff<bf16, BKV>(D + rr, col)] = val;
+  }
+  __syncthreads();
+  bf16x8 q_frag[D / 32];
+  {
+    const int r = lane & 15;
+#pragma unroll
+    for (int ks = 0; ks < D / 32; ++ks) {
+      const int kb = ks * 32 + (lane >> 4) * 8;
+      q_frag[ks] = *(const bf16x8*)&q_lds[aoff<bf16, D>(r, kb)];
+    }
+  }
+  __syncthreads();  // q_lds free -> p_lds
+
+  float m_run[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m_run[j] = -INFINITY;
+  f32x4 o_acc[FO + 1] = {};  // acc[FO] col 0 = running softmax denominator
+  TStage<BKV, D, 64> vst;
+
+  stage_tile<BKV, D, 1>(k + (int64_t)t0 * BKV * D, k_lds[0],
+                        kv_len - t0 * BKV, zero16);
+  vst.load(v + (int64_t)t0 * BKV * D, kv_len - t0 * BKV);
+  vst.write(vt_lds[0]);
+  __syncthreads();
+
+  for (int t = t0; t < t1; ++t) {
+    const int cur = (t - t0) & 1;
+    const int kv0 = t * BKV;
+    if (t + 1 < t1) {
+      stage_tile<BKV, D, 1>(k + (int64_t)(kv0 + BKV) * D, k_lds[cur ^ 1],
+                            kv_len - kv0 - BKV, zero16);
+      vst.load(v + (int64_t)(kv0 + BKV) * D, kv_len - kv0 - BKV);
+    }
+
+    f32x4 s_acc[FN] = {};
+    mma_nt_areg<D, FN>(q_frag, k_lds[cur], lane, s_acc);
+
+    float alpha[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int last = p0 + cr + j;  // newest key this row sees
+      float mx = -INFINITY;
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn) {
+        int gcol = kv0 + fn * 16 + cc;
+        float sv = s_acc[fn][j] * scale;
+        if (gcol >= kv_len || gcol > last) sv = -INFINITY;
+        s_acc[fn][j] = sv;
+        mx = fmaxf(mx, sv);
+      }
+      mx = row_reduce_max(mx);
+      float m_new = fmaxf(m_run[j], mx);
+      // all-masked row in this tile (last < kv0): keep everything unchanged
+      float a = (m_new == -INFINITY) ? 1.0f : __expf(m_run[j] - m_new);
+      if (m_run[j] == -INFINITY) a = 0.0f;
+      if (m_new == -INFINITY) a = 1.0f;
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn) {
+        float p = (s_acc[fn][j] == -INFINITY) ? 0.0f
+                                              : __expf(s_acc[fn][j] - m_new);
+        s_acc[fn][j] = p;
+      }
+      m_run[j] = m_new;
+      alpha[j] = a;
+    }
+    frag_to_lds<FN>(s_acc, p_lds, lane);
+#pragma unroll
+    for (int fo = 0; fo <= FO; ++fo)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o_acc[fo][j] *= alpha[j];
+    mma_pv<FO + 1>(p_lds, vt_lds[cur], 0, lane, o_acc);
+
+    if (t + 1 < t1)
+      vst.write(vt_lds[cur ^ 1]);
+    __syncthreads();
+  }
+
+  // unnormalised partials; the denominator sits in col 0 of acc[FO]
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int row = cr + j;
+#pragma unroll
+    for (int fo = 0; fo < FO; ++fo)
+      pob[row * D + fo * 16 + cc] = o_acc[fo][j];
+    if (cc == 0) {
+      mlb[row * 2] = m_run[j];
+      mlb[row * 2 + 1] = o_acc[FO][j];
+    }
+  }
+}
+
+// Folds the NS partials of k_attn_ext_split in index order (max of m, then
+// weights exp(m_s - m), splits with l_s == 0 skipped, as k_attn_decode_fin)
+// and stores bf16 o through the o strides: rows >= n and rows with l == 0
+// as zeros. Grid (B*H), 256 threads over the T x D outputs.
+template <int D>
+__launch_bounds__(256)
+__global__ void k_attn_ext_fin(const float* __restrict__ po,
+                               const float* __restrict__ ml,
+                               bf16* __restrict__ O,
+                               const int64_t* __restrict__ pos,
+                               const int64_t* __restrict__ n_new, int T,
+                               int cap, int H, int NS, int64_t o_rs,
+                               int64_t o_hs, int64_t o_bs) {
+  const int64_t bh = blockIdx.x;
+  const int64_t b = bh / H, h = bh % H;
+  const int p0 = (int)min(max(pos[b], (int64_t)0), (int64_t)cap);
+  const int n = (int)min(max(n_new ? n_new[b] : (int64_t)T, (int64_t)0),
+                         (int64_t)min(T, cap - p0));
+  bf16* o = O + b * o_bs + h * o_hs;
+  const float* pob = po + bh * NS * 16 * D;
+  const float* mlb = ml + bh * NS * 16 * 2;
+  for (int e = threadIdx.x; e < T * D; e += 256) {
+    const int row = e / D, d = e % D;
+    float acc = 0.0f, l = 0.0f;
+    if (row < n) {
+      float m = -INFINITY;
+      for (int s = 0; s < NS; ++s) m = fmaxf(m, mlb[(s * 16 + row) * 2]);
+      for (int s = 0; s < NS; ++s) {
+        const float ms = mlb[(s * 16 + row) * 2];
+        const float ls = mlb[(s * 16 + row) * 2 + 1];
+        if (ls > 0.0f) {
+          const float w = __expf(ms - m);
+          l += ls * w;
+          acc += pob[(s * 16 + row) * D + d] * w;
+        }
+      }
+    }
+    o[(int64_t)row * o_rs + d] = f2bf(l > 0.0f ? acc / l : 0.0f);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Di = rowsum(dO * O) per (b,h,row)
 __global__ void k_attn_dot(const bf16* __restrict__ dO,
                            const bf16* __restrict__ O, float* __restrict__ Di,
@@ -830,6 +1033,61 @@ void attn_ext_launch(const void* q, const void* k, const void* v, void* o,
   else if (D == 128) PICK(128);
 #undef PICK
 #undef LAUNCH
+}
+
+// Split-KV extend attention (T <= 16): NS one-wave blocks per (b, h) walk
+// disjoint runs of the live KV tiles, k_attn_ext_fin folds them. The grid,
+// (NS, B*H) then (B*H), is fixed by shapes alone.
+void attn_ext_split_launch(const void* q, const void* k, const void* v,
+                           void* o, float* po, float* ml, const int64_t* pos,
+                           const int64_t* n_new, const void* zero16, int B,
+                           int H, int T, int cap, int D, int NS,
+                           const int64_t* q_str, const int64_t* o_str,
+                           float scale, hipStream_t s) {
+#define LAUNCH(DD)                                                           \
+  do {                                                                       \
+    hipLaunchKernelGGL((k_attn_ext_split<DD>), dim3(NS, B * H), dim3(64), 0, \
+                       s, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
+                       po, ml, pos, n_new, (const bf16*)zero16, T, cap, H,   \
+                       q_str[0], q_str[1], q_str[2], scale);                 \
+    hipLaunchKernelGGL((k_attn_ext_fin<DD>), dim3(B * H), dim3(256), 0, s,   \
+                       po, ml, (bf16*)o, pos, n_new, T, cap, H, NS,          \
+                       o_str[0], o_str[1], o_str[2]);                        \
+  } while (0)
+  if (D == 64) LAUNCH(64);
+  else if (D == 128) LAUNCH(128);
+#undef LAUNCH
+}
+
+// Split count of the automatic route (BatchedDecoder.verify); 0 = the
+// unsplit k_attn_ext. A function of shapes alone: the prefix length lives
+// on the device. Measured (profiles/spec_decode_r1.md): on a prefix of half
+// the cache or more, splitting pays 1.3x .. 2.6x
+//   * with about four KV tiles or more per split: four splits at cap 1024,
+//     eight at cap 4096; past that the prologue and the combine outweigh
+//     the one or two tiles left per block (16 splits never won);
+//   * as long as B*H*NS stays within the ~1024 one-wave blocks the device
+//     holds at once (four per CU at D=64): a second round of blocks costs
+//     more than the shorter walk saves. This is attn_decode's ragged rule,
+//     1024 / (B*H), kept as the ceiling.
+//
+//     T          KV tiles of cap   splits
+//     17 ..      any               0 (unsplit)
+//     1 .. 16    1 .. 3            0 (unsplit)
+//     1 .. 16    4 ..              min(ceil(tiles / 2),
+//                                      clamp(tiles / 8, 4, 8),
+//                                      1024 / (B*H)); 0 if that is below 2
+//
+// A prefix of one or two tiles is faster unsplit whatever the count (the
+// combine is a second launch: 10 .. 13 us against 7 .. 10 us), which a rule
+// of shapes cannot see; caches that short stay unsplit.
+int attn_ext_splits(int64_t BH, int64_t cap, int64_t T) {
+  if (T > 16 || T < 1 || BH < 1) return 0;
+  const int64_t tiles = (cap + BKV - 1) / BKV;
+  if (tiles < 4) return 0;
+  int64_t ns = std::max<int64_t>(4, std::min<int64_t>(8, tiles / 8));
+  ns = std::min(ns, std::min((tiles + 1) / 2, 1024 / BH));
+  return ns < 2 ? 0 : (int)ns;
 }
 
 // dense fp32 [B,H,S,D] workspace -> strided bf16 dq (w_* tuple)

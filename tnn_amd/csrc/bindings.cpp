@@ -1610,11 +1610,15 @@ static void ext_check_rows(const char* fn, const char* name,
 // caches. Sequence b attends rows i < n_new[b] (all T when absent) at
 // positions pos[b] + i over keys [0, pos[b] + i]; rows >= n_new[b] come
 // back zero. o is [B,H,T,D] over [B,T,H,D] memory: o.transpose(1, 2) is
-// contiguous.
+// contiguous. kv_splits == 0 runs k_attn_ext; kv_splits in [1, 16] (T <= 16
+// only) runs the split-KV form with that many blocks per (b, h).
 at::Tensor attn_extend(const at::Tensor& q, const at::Tensor& k_cache,
                        const at::Tensor& v_cache, const at::Tensor& pos,
-                       const c10::optional<at::Tensor>& n_new, double scale) {
+                       const c10::optional<at::Tensor>& n_new, double scale,
+                       int64_t kv_splits) {
   const char* fn = "attn_extend";
+  TORCH_CHECK(kv_splits >= 0 && kv_splits <= 16, fn,
+              ": kv_splits must be in [0, 16], got ", kv_splits);
   ext_check_caches(fn, k_cache, v_cache);
   TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16, fn,
               ": bf16 only, got ", k_cache.scalar_type());
@@ -1628,8 +1632,25 @@ at::Tensor attn_extend(const at::Tensor& q, const at::Tensor& k_cache,
   ext_check_index(fn, "pos", pos, k_cache);
   if (n_new.has_value()) ext_check_index(fn, "n_new", *n_new, k_cache);
   const int64_t T = q.size(2);
+  TORCH_CHECK(kv_splits == 0 || T <= 16, fn,
+              ": kv_splits >= 1 wants T <= 16, got T = ", T);
   auto o_buf = at::empty({B, T, H * D}, q.options());
   auto o = o_buf.view({B, T, H, D}).permute({0, 2, 1, 3});
+  if (kv_splits >= 1) {
+    auto po = at::empty({B * H, kv_splits, 16, D},
+                        q.options().dtype(at::kFloat));
+    auto ml = at::empty({B * H, kv_splits, 16, 2},
+                        q.options().dtype(at::kFloat));
+    attn_ext_split_launch(
+        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+        o_buf.data_ptr(), po.data_ptr<float>(), ml.data_ptr<float>(),
+        pos.data_ptr<int64_t>(),
+        n_new.has_value() ? n_new->data_ptr<int64_t>() : nullptr,
+        zero_page(q), (int)B, (int)H, (int)T, (int)cap, (int)D,
+        (int)kv_splits, attn_strides(q).data(), attn_strides(o).data(),
+        (float)scale, cur_stream());
+    return o;
+  }
   attn_ext_launch(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                   o_buf.data_ptr(), pos.data_ptr<int64_t>(),
                   n_new.has_value() ? n_new->data_ptr<int64_t>() : nullptr,
@@ -1794,7 +1815,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("smax_bwd", &tnn::smax_bwd);
   m.def("attn_decode", &tnn::attn_decode);
   m.def("kv_append", &tnn::kv_append);
-  m.def("attn_extend", &tnn::attn_extend);
+  m.def("attn_extend", &tnn::attn_extend, py::arg("q"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("pos"), py::arg("n_new"),
+        py::arg("scale"), py::arg("kv_splits") = 0);
+  m.def("attn_extend_splits", &tnn::attn_ext_splits, py::arg("BH"),
+        py::arg("cap"), py::arg("T"));
   m.def("kv_append_n", &tnn::kv_append_n);
   m.def("sample_logits", &tnn::sample_logits, py::arg("logits"),
         py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),

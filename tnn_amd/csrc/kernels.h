@@ -310,6 +310,16 @@ void attn_ext_launch(const void* q, const void* k, const void* v, void* o,
                      const void* zero16, int B, int H, int T, int cap, int D,
                      const int64_t* q_str, const int64_t* o_str, float scale,
                      hipStream_t s);
+// split-KV form for T <= 16: NS blocks per (b, h) over the live prefix; po
+// [B*H, NS, 16, D] and ml [B*H, NS, 16, 2] are uninitialised fp32 workspaces
+void attn_ext_split_launch(const void* q, const void* k, const void* v,
+                           void* o, float* po, float* ml, const int64_t* pos,
+                           const int64_t* n_new, const void* zero16, int B,
+                           int H, int T, int cap, int D, int NS,
+                           const int64_t* q_str, const int64_t* o_str,
+                           float scale, hipStream_t s);
+// split count the automatic route uses for (B*H, cap, T); 0 = unsplit
+int attn_ext_splits(int64_t BH, int64_t cap, int64_t T);
 
 // ---- bmm.hip ---------------------------------------------------------------
 void bmm_launch(DT dt, const void* a, const void* b, void* c,

@@ -183,6 +183,9 @@ class BatchedDecoder:
     ``extend(chunks)`` appends several tokens per row at each row's own
     position (a further turn, a refilled row, a prompt in pieces, draft
     tokens) and ``rewind(lengths)`` sets the positions back.
+    ``verify(chunks)`` is ``extend`` for a block of draft tokens: the same
+    forward on the split-KV extend kernel, returning the greedy token after
+    every fed token (``generate_speculative``).
     """
 
     def __init__(self, model: Sequential, seq_len: int = 1024,
@@ -230,7 +233,8 @@ class BatchedDecoder:
             p._pos_tensor = self.pos
 
     @torch.no_grad()
-    def extend(self, chunks: List[List[int]]) -> torch.Tensor:
+    def extend(self, chunks: List[List[int]],
+               kv_splits: int = 0) -> torch.Tensor:
         """Append ``chunks[b]`` to row b at its own position: one eager
         forward over the right-padded ``[B, Tmax]`` batch, every row
         attending over its own cache prefix, the chunk lengths on the
@@ -241,7 +245,15 @@ class BatchedDecoder:
         ``ValueError``, with nothing changed, if a row would pass
         ``seq_len`` (the positions are read back: one sync). Positions
         stay clamped to ``seq_len - 1`` like everywhere in this class, so
-        a row filled to the brim reads as one short of it."""
+        a row filled to the brim reads as one short of it. ``kv_splits``
+        goes to ``ops.attention_extend`` (0: the unsplit kernel)."""
+        x, n_new = self._extend_input(chunks)
+        logits = self._extend_logits(x, n_new, kv_splits)
+        return logits[torch.arange(x.shape[0], device=self.device),
+                      (n_new - 1).clamp(min=0)]
+
+    def _extend_input(self, chunks: List[List[int]]):
+        """Checked, right-padded ``[B, Tmax]`` tokens and device lengths."""
         if self.pos is None:
             raise RuntimeError("extend wants open() or prefill() first")
         B = self.pos.numel()
@@ -258,8 +270,17 @@ class BatchedDecoder:
         x = torch.tensor([list(c) + [0] * (tmax - len(c)) for c in chunks],
                          dtype=torch.int64, device=self.device)
         n_new = torch.tensor(lens, dtype=torch.int64, device=self.device)
+        return x, n_new
+
+    def _extend_logits(self, x: torch.Tensor, n_new: torch.Tensor,
+                       kv_splits) -> torch.Tensor:
+        """The extend forward over ``x [B, Tmax]`` with ``n_new [B]`` live
+        tokens per row: ``[B, Tmax, V]`` logits, positions advanced.
+        ``kv_splits`` is a count, or a callable giving each attention
+        block its own."""
         for a in self._attns:
-            a.set_extend(True, n_new)
+            a.set_extend(True, n_new,
+                         kv_splits(a) if callable(kv_splits) else kv_splits)
         for p in self._poss:
             p._extend = True
         try:
@@ -269,10 +290,46 @@ class BatchedDecoder:
                 a.set_extend(False)
             for p in self._poss:
                 p._extend = False
-        out = logits[torch.arange(B, device=self.device),
-                     (n_new - 1).clamp(min=0)]
         self.pos.add_(n_new).clamp_(max=self.seq_len - 1)
-        return out
+        return logits
+
+    def _verify_splits(self, tmax: int):
+        """Per attention block, the split count of the automatic route:
+        ``ext.attn_extend_splits`` where the bf16 extend kernel runs, 0
+        elsewhere."""
+        B = self.pos.numel()
+
+        def splits(a) -> int:
+            if not (self.device.type == "cuda"
+                    and a.wq.dtype == torch.bfloat16
+                    and a.head_dim in (64, 128)):
+                return 0
+            from .. import _C
+            return _C.ext().attn_extend_splits(B * a.num_heads, self.seq_len,
+                                               tmax)
+        return splits
+
+    @torch.no_grad()
+    def verify(self, chunks: List[List[int]]) -> torch.Tensor:
+        """The forward of ``extend`` for a block of draft tokens, on the
+        split-KV extend kernel where the bf16 GPU route runs (split count
+        from ``ext.attn_extend_splits``). Returns the greedy token after
+        every fed token, int64 ``[B, Tmax]`` on the device
+        (``ops.sample_logits`` at temperature 0: the lowest index among
+        the maxima, as in the captured decode step); entries at and beyond
+        a row's chunk length mean nothing. Positions advance as in
+        ``extend``; the caller rewinds to what it accepts."""
+        x, n_new = self._extend_input(chunks)
+        return self._verify(x, n_new)
+
+    def _verify(self, x: torch.Tensor, n_new: torch.Tensor) -> torch.Tensor:
+        """``verify`` on device tensors, unchecked: the caller vouches that
+        no row passes ``seq_len`` (no position read-back)."""
+        from ..ops import sample_logits
+        B, tmax = x.shape
+        logits = self._extend_logits(x, n_new, self._verify_splits(tmax))
+        return sample_logits(logits.reshape(B * tmax, -1),
+                             temperature=0).reshape(B, tmax)
 
     def rewind(self, lengths: List[int]) -> None:
         """Set every row's position. Cache slots at and above a row's
@@ -432,6 +489,197 @@ def generate_batch(model: Sequential, prompts: List[List[int]],
     for c0 in range(0, len(live), MAX_DECODE_BATCH):
         run_chunk(live[c0:c0 + MAX_DECODE_BATCH])
     return out
+
+
+def _vocab_and_positions(model: Sequential):
+    """(vocabulary size, shortest positional table) of a GPT-style model."""
+    from ..nn.layers import Embedding, PositionalEmbedding
+    vocab = [m.vocab_size for m in model.modules() if isinstance(m, Embedding)]
+    plen = [m.max_len for m in model.modules()
+            if isinstance(m, PositionalEmbedding)]
+    return (vocab[0] if vocab else None), (min(plen) if plen else None)
+
+
+@torch.no_grad()
+def _speculative_chunk(tgt: BatchedDecoder, drf: BatchedDecoder,
+                       prompts: List[List[int]], n_new: List[int], k: int,
+                       eot_token: Optional[int], use_graph: Optional[bool]):
+    """Greedy draft/verify rounds for one batch of live rows (every
+    ``n_new[b] >= 1``). Returns the new ids per row and (rounds, drafted,
+    accepted). Invariant at the top of a round: both caches hold row b's
+    first ``L_b`` tokens, both position tensors read ``L_b``, and the
+    pending token (sampled, in neither cache) sits in ``pending``."""
+    from ..ops import sample_logits
+    device, seq_len = tgt.device, tgt.seq_len
+    B = len(prompts)
+    graphed = device.type == "cuda" if use_graph is None else use_graph
+
+    logits = tgt.prefill(prompts)
+    drf.prefill(prompts)
+    pending = sample_logits(logits, temperature=0).reshape(B, 1)
+
+    # the draft's single-token step, as _decode_loop captures its own:
+    # forward, greedy pick, record, feed-back, advance
+    step_t = torch.zeros(1, dtype=torch.int64, device=device)
+    static_tok = pending.clone()
+    # two spare columns: the graph warm-up steps record past the end
+    d_buf = torch.zeros(B, k + 3, dtype=torch.int64, device=device)
+
+    def step():
+        nxt = sample_logits(drf.forward_token(static_tok),
+                            temperature=0).reshape(B, 1)
+        d_buf.index_copy_(1, step_t, nxt)
+        static_tok.copy_(nxt)
+        step_t.add_(1)
+        drf.advance()
+
+    graph = None
+    if graphed:
+        state = (drf.pos, static_tok, d_buf, step_t)
+        saved = [t.clone() for t in state]
+        stream = torch.cuda.Stream()
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            for _ in range(2):  # warmup; stale cache rows stay masked
+                step()
+        torch.cuda.current_stream().wait_stream(stream)
+        for t, s0 in zip(state, saved):
+            t.copy_(s0)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            step()
+        for t, s0 in zip(state, saved):
+            t.copy_(s0)
+
+    first = pending[:, 0].tolist()
+    new: List[List[int]] = [[t] for t in first]
+    length = [len(p) for p in prompts]      # L_b, mirrored on the host
+    done = [n_new[b] <= 1 or (eot_token is not None and first[b] == eot_token)
+            for b in range(B)]
+    rounds, drafted, accepted = 0, [0] * B, [0] * B
+    col = torch.arange(k + 1, device=device)
+
+    while not all(done):
+        rounds += 1
+        # 1. draft: k + 1 single-token steps from the pending token, the
+        # last only to put d_k into the draft's cache
+        static_tok.copy_(pending)
+        step_t.zero_()
+        for _ in range(k + 1):
+            if graph is not None:
+                graph.replay()
+            else:
+                step()
+        # 2. verify [pending, d_1 .. d_k], cut to the slots a row has left
+        lens = [0 if done[b] else min(k + 1, seq_len - length[b])
+                for b in range(B)]
+        tmax = max(lens)
+        lens_t = torch.tensor(lens, dtype=torch.int64, device=device)
+        # (a finished row may have been filled to the brim: keep it in bounds)
+        old = torch.tensor([min(n, seq_len - 1) for n in length],
+                           dtype=torch.int64, device=device)
+        x = torch.cat([pending, d_buf[:, :k]], 1)[:, :tmax]
+        # padding reads as token 0, as in extend
+        x = torch.where(col[None, :tmax] < lens_t[:, None], x,
+                        torch.zeros_like(x))
+        tgt.pos.copy_(old)
+        t_tok = tgt._verify(x, lens_t)                       # [B, tmax]
+        # 3. accept: j leading drafts that the target would have picked
+        ok = (x[:, 1:] == t_tok[:, :-1]) & \
+            (col[None, 1:tmax] < lens_t[:, None])
+        j = ok.long().cumprod(1).sum(1, keepdim=True)        # [B, 1]
+        emit = torch.where(col[None, :tmax] < j,
+                           torch.cat([x[:, 1:], x[:, :1]], 1), t_tok)
+        pending = t_tok.gather(1, j)
+        live_t = lens_t > 0
+        new_pos = torch.where(live_t, old + j[:, 0] + 1, old) \
+            .clamp_(max=seq_len - 1)
+        tgt.pos.copy_(new_pos)
+        drf.pos.copy_(new_pos)
+        # 4. the round's one read-back
+        back = torch.cat([emit, j], 1).tolist()
+        for b in range(B):
+            if done[b]:
+                continue
+            jb = back[b][tmax]
+            ids = back[b][:jb + 1]
+            drafted[b] += lens[b] - 1
+            accepted[b] += jb
+            length[b] += jb + 1
+            room = n_new[b] - len(new[b])
+            ids = ids[:room]
+            if eot_token is not None and eot_token in ids:
+                ids = ids[:ids.index(eot_token) + 1]
+                done[b] = True
+            new[b] += ids
+            if len(new[b]) >= n_new[b]:
+                done[b] = True
+    return new, (rounds, drafted, accepted)
+
+
+@torch.no_grad()
+def generate_speculative(target: Sequential, draft: Sequential,
+                         prompts: List[List[int]], max_new_tokens: int = 50,
+                         k: int = 4, seq_len: int = 1024,
+                         eot_token: Optional[int] = 50256,
+                         device: Optional[torch.device] = None,
+                         use_graph: Optional[bool] = None,
+                         return_stats: bool = False):
+    """Greedy speculative decode of a ragged batch: a small ``draft`` model
+    proposes ``k`` tokens per row and round with its single-token step
+    (captured once as a hipGraph and replayed), the ``target`` checks them
+    in one ``BatchedDecoder.verify`` forward (split-KV extend attention on
+    the bf16 GPU route) and each row keeps the drafts up to the first one
+    the target would not have picked, plus the target's own token there:
+    1 to ``k + 1`` tokens per target forward. Acceptance and the position
+    updates stay on the device; the emitted tokens are read back once per
+    round.
+
+    Contract: for any draft, in fp32 the result equals
+    ``generate_batch(target, prompts, greedy=True, ...)`` token for token,
+    with its length rule (``min(max_new_tokens, seq_len - len)``, rows
+    without room returned unchanged) and EOT truncation. More than 16
+    prompts run in chunks of 16. ``1 <= k <= 15``. ``ValueError`` before
+    any cache exists for differing vocabularies, a draft whose positional
+    table is shorter than ``seq_len``, ``k`` out of range or an empty
+    prompt. ``return_stats=True`` also returns ``{"rounds", "drafted",
+    "accepted"}``, the last two per row. Greedy only: sampled speculative
+    decoding (rejection sampling over both distributions) is not built."""
+    prompts = [list(p) for p in prompts]
+    if any(len(p) == 0 for p in prompts):
+        raise ValueError("generate_speculative: empty prompt")
+    if not 1 <= k <= 15:
+        raise ValueError(f"k must be in 1..15, got {k}")
+    (tv, _), (dv, dpos) = (_vocab_and_positions(m) for m in (target, draft))
+    if tv != dv:
+        raise ValueError(f"target and draft vocabularies differ: {tv} vs {dv}")
+    if dpos is not None and dpos < seq_len:
+        raise ValueError(f"the draft's positional table ({dpos}) is shorter "
+                         f"than seq_len {seq_len}")
+    device = device or next(target.parameters()).device
+    n_new = [min(max_new_tokens, seq_len - len(p)) for p in prompts]
+    out = [list(p) for p in prompts]
+    live = [i for i, n in enumerate(n_new) if n > 0]
+    stats = {"rounds": 0, "drafted": [0] * len(prompts),
+             "accepted": [0] * len(prompts)}
+
+    for c0 in range(0, len(live), MAX_DECODE_BATCH):
+        rows = live[c0:c0 + MAX_DECODE_BATCH]
+        tgt = BatchedDecoder(target, seq_len, device)
+        drf = BatchedDecoder(draft, seq_len, device)
+        try:
+            new, (rounds, drafted, accepted) = _speculative_chunk(
+                tgt, drf, [prompts[i] for i in rows],
+                [n_new[i] for i in rows], k, eot_token, use_graph)
+        finally:
+            tgt.close()
+            drf.close()
+        stats["rounds"] += rounds
+        for r, i in enumerate(rows):
+            out[i] = prompts[i] + new[r]
+            stats["drafted"][i] = drafted[r]
+            stats["accepted"][i] = accepted[r]
+    return (out, stats) if return_stats else out
 
 
 class DecodeSession:

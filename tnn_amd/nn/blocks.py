@@ -299,15 +299,18 @@ class _MHABase(Layer):
         self._kv_cache = {"k": None, "v": None, "len": 0, "cap": max_len,
                           "pos_t": pos_t}
 
-    def set_extend(self, on: bool, n_new: Optional[torch.Tensor] = None):
+    def set_extend(self, on: bool, n_new: Optional[torch.Tensor] = None,
+                   kv_splits: int = 0):
         """Extend mode of the per-sequence static cache: a forward over
         ``[B, T]`` appends row b's first ``n_new[b]`` tokens (all T when
         None) at ``pos_t[b]`` and attends each over its own prefix
         (``_extend_forward``). Off, multi-token input keeps the prefill
-        route, which writes at one shared host position."""
+        route, which writes at one shared host position. ``kv_splits``
+        goes to ``ops.attention_extend`` (0: the unsplit kernel)."""
         c = self._kv_cache
         assert c is not None and "pos_t" in c and c["pos_t"].numel() >= 1
         c["extend"], c["n_new"] = on, n_new if on else None
+        c["kv_splits"] = kv_splits if on else 0
 
     def _extending(self) -> bool:
         c = self._kv_cache
@@ -335,7 +338,7 @@ class _MHABase(Layer):
             c["v"] = torch.zeros_like(c["k"])
         ops.kv_append_n(c["k"], c["v"], k, v, c["pos_t"], c["n_new"])
         o = ops.attention_extend(q, c["k"], c["v"], c["pos_t"], c["n_new"],
-                                 hd ** -0.5)
+                                 hd ** -0.5, c.get("kv_splits", 0))
         o = o.transpose(1, 2).reshape(b, s, d)   # [B,T,H,D] memory: a view
         return ops.linear(o, self.wo, self.bo, residual=residual)
 

@@ -1184,7 +1184,8 @@ def _extend_extent(pos: torch.Tensor, n_new: Optional[torch.Tensor],
 def attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, pos: torch.Tensor,
                      n_new: Optional[torch.Tensor] = None,
-                     scale: Optional[float] = None) -> torch.Tensor:
+                     scale: Optional[float] = None,
+                     kv_splits: int = 0) -> torch.Tensor:
     """Attention of T new query rows per sequence against that sequence's
     own cache prefix (inference only). q ``[B,H,T,D]`` (unit d-stride; the
     head slices of a merged projection are fine), caches ``[B,H,cap,D]``
@@ -1195,13 +1196,16 @@ def attention_extend(q: torch.Tensor, k_cache: torch.Tensor,
     never enter the result, whatever they hold. Returns ``[B,H,T,D]`` laid
     out ``[B,T,H,D]``, so ``o.transpose(1, 2)`` is contiguous. CUDA bf16
     with D in {64, 128} runs the flash extend kernel; everything else the
-    torch form of the same rule."""
+    torch form of the same rule. ``kv_splits >= 1`` (T <= 16, at most 16)
+    runs the kernel's split-KV form with that many blocks per (b, h) over
+    the live prefix; the torch form ignores it."""
     B, H, T, D = q.shape
     cap = k_cache.shape[2]
     if scale is None:
         scale = D ** -0.5
     if q.is_cuda and q.dtype == torch.bfloat16 and D in (64, 128):
-        return _C.ext().attn_extend(q, k_cache, v_cache, pos, n_new, scale)
+        return _C.ext().attn_extend(q, k_cache, v_cache, pos, n_new, scale,
+                                    kv_splits)
     p0, n = _extend_extent(pos, n_new, T, cap)
     i = torch.arange(T, device=q.device)
     j = torch.arange(cap, device=q.device)
